@@ -20,8 +20,14 @@ Multi-GPU (one rank per GPU): under torch.distributed.run (WORLD_SIZE set), or w
 `--gpus N` alone, which starts the N ranks itself (before anything touches the GPU).
 Every rank holds the whole index, searches its own K batches of reads (weak scaling,
 no collective on the data path), checks a sample of its timed reads against the CPU
-restatement, and the per-rank hit lists of every timed read set are gathered to rank 0
+restatement (`--full`), and the per-rank hit lists of every timed read set are gathered to rank 0
 over RCCL after timing; rank 0 re-checks the gathered lists against per-rank digests.
+
+A plain run (`--gpus 1 --steps K --warmup W`) does what the headline figure needs: it
+builds the index and the read sets, warms up, times the K steps, writes the last
+step's results if `--dump-outputs DIR` is given (dump_outputs) and prints the result
+line.  Everything below, and the roofline (gather probes, serialized steps), the steps
+with the copies inside, the drop-in legs and the parity checks, runs with `--full` only.
 
 Baselines beside the GPU figure (rank 0 at N=1, configs 2 and 3): the restatement on
 the box's CPU share (the whole timed batch, also the parity check), and the
@@ -385,6 +391,45 @@ def batch_digest(n_aln, flags, hits_ordered):
     h.update((np.asarray(flags, np.uint32) & 1).astype(np.uint32).tobytes())
     h.update(np.ascontiguousarray(hits_ordered, np.uint32).tobytes())
     return h.hexdigest()
+
+
+DUMP_HIT_BYTES = 40 << 20   # --dump-outputs: the hit records' share of its 64 MB
+DUMP_SEED = 20240
+
+
+def dump_outputs(d, suffix, n_aln, flags, hit_off, hits, res=None):
+    """--dump-outputs DIR: one step's results as a caller of the device path reads them,
+    as DIR/<name>.npy, in a form two builds can be compared by.  The kernel appends each
+    read's hits wherever its atomic lands, so the hit records are written in read order
+    (hits_in_read_order: what hit_off says, without its run-to-run values) and hit_off
+    itself is not written.
+      n_aln.npy     float32 (reads,)     hits per read
+      fallback.npy  float32 (reads,)     the splice-fallback flag (bit 0 of flags)
+      hit_reads.npy float64 (m,)         the reads whose hit records are written: all of
+                                         them, or a fixed seeded sample (ascending) cut to
+                                         DUMP_HIT_BYTES of records
+      hits.npy      float64 (k, words)   those reads' hit records, every u32 word, read order
+      splice.npy    float64 (m, words)   config 4: the splice path's answers of hit_reads
+    Under 64 MB in all at the bench's batch sizes."""
+    os.makedirs(d, exist_ok=True)
+    n = len(n_aln)
+    cnt = np.maximum(np.asarray(n_aln, np.int64), 0)
+    words = hits.shape[1] + (res.shape[1] if res is not None else 0)
+    cap = DUMP_HIT_BYTES // (8 * words)
+    sel = np.arange(n)
+    if int(cnt.sum()) + (n if res is not None else 0) > cap:
+        sel = np.sort(np.random.default_rng(DUMP_SEED).permutation(n)[:max(1, n // 4)])
+        cost = np.cumsum(cnt[sel] + (1 if res is not None else 0))
+        sel = sel[:int(np.searchsorted(cost, cap, side="right"))]
+    h = hits_in_read_order(cnt[sel], np.asarray(hit_off, np.int64)[sel], hits)
+    out = {"n_aln": np.asarray(n_aln, np.float32), "fallback": (np.asarray(flags) & 1).astype(np.float32),
+           "hit_reads": sel.astype(np.float64), "hits": h.astype(np.float64)}
+    if res is not None:
+        out["splice"] = res[sel].astype(np.float64)
+    for k, v in out.items():
+        np.save(os.path.join(d, f"{k}{suffix}.npy"), v)
+    log(f"[bench] outputs of the last timed step written to {d}: "
+        + ", ".join(f"{k}{suffix}.npy {v.shape}" for k, v in out.items()))
 
 
 # ---------------------------------------------------------------- the reference's own path
@@ -771,7 +816,18 @@ def main():
                     help="fixed-total mode (strong scaling, BASELINE configs[2] as stated: e.g. --config 3 "
                          "--total-reads 10000000): the reads in the reference's 100 000-read batches dealt over the "
                          "ranks, host-array bwa_cal_sa_reg_gap semantics, gather timed apart (fixed_total)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the gather probes and the serialized "
+                         "roofline steps, the steps with the copies inside, the drop-in legs, the parity checks and "
+                         "the CPU baselines (restatement and reference).  Without it a run sets up, warms up, times "
+                         "the steps and prints the result line; the options of those legs then have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(dump_outputs)")
     a = ap.parse_args()
+    if not a.full:
+        a.cpu_sample = a.parity_sample = a.ref_sample = a.e2e_reads = a.dropin = a.copies = 0
+        a.roofline_steps = a.rank_parity = 0
     if a.streams <= 0:
         # three handles where three handles' scratch fits: config 2 +1.8 % (profiles/r05_streams3_ab.log),
         # config 3 +0.8-1.6 % with its 16 384-entry pools (profiles/r05_pool16k_ab.log)
@@ -841,8 +897,8 @@ def main():
     recs = synth.record_layout(T, RECORDS)
     nb = a.warmup + a.steps
     nd = min(nb, DISTINCT)
-    batches = []
-    for j in range(nd):
+
+    def read_set(j):
         gidx = j * world + rank
         if a.config == 2:
             reads, _ = synth.make_reads(genome, recs, a.batch, READ_LEN, 5 * 1_000_000 + gidx, max_mm=4)
@@ -853,7 +909,12 @@ def main():
         else:   # SURVEY §8d config 3 reads (seed 6): one indel of 1-3 bp + 0-2 substitutions
             reads, _ = synth.make_reads(genome, recs, a.batch, READ_LEN, 6 * 1_000_000 + gidx, indel=True,
                                         max_mm_indel=2)
-        batches.append(reads)
+        return reads
+
+    # the read sets are independent (counter-based generators): one host thread each
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(nd) as ex:
+        batches = list(ex.map(read_set, range(nd)))
     log(f"[bench] rank {rank}: {nd} x {a.batch} reads generated in {time.time() - t0:.1f} s")
 
     # bwa_cal_sa_reg_gap prologue on the host (bwtaln.c:254-337): -n 4 -o 0|1, fixed length.
@@ -913,11 +974,15 @@ def main():
 
     # the measured ceiling for this access pattern: random whole 64-B blocks over a
     # table as large as the rank index (before the timed region, same process)
-    rand_gbs = _lib.probe_gather(gi.nbytes(), 1, device)
-    rand64_gbs = _lib.probe_gather(gi.nbytes(), 4, device)
-    coop_gbs = _lib.probe_gather(gi.nbytes(), 2, device)
-    log(f"[bench] rank {rank}: random-sector gather probe over {gi.nbytes() / 2**30:.2f} GiB: {rand_gbs:.0f} GB/s "
-        f"(16-B loads), {coop_gbs:.0f} GB/s (4 lanes x 16 B per sector), {rand64_gbs:.0f} GB/s (whole sectors per lane)")
+    # (--full: the roofline's yardstick)
+    rand_gbs = rand64_gbs = coop_gbs = None
+    if a.full:
+        rand_gbs = _lib.probe_gather(gi.nbytes(), 1, device)
+        rand64_gbs = _lib.probe_gather(gi.nbytes(), 4, device)
+        coop_gbs = _lib.probe_gather(gi.nbytes(), 2, device)
+        log(f"[bench] rank {rank}: random-sector gather probe over {gi.nbytes() / 2**30:.2f} GiB: {rand_gbs:.0f} "
+            f"GB/s (16-B loads), {coop_gbs:.0f} GB/s (4 lanes x 16 B per sector), {rand64_gbs:.0f} GB/s (whole "
+            f"sectors per lane)")
 
     # a handle past the second whose search scratch does not fit (a gapped regime's pool
     # is ~95 GB per handle at config 3) is dropped before the timed region
@@ -957,6 +1022,13 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     kms = [e0.elapsed_time(e1) for e0, e1 in ev]
+    if a.dump_outputs:                        # before any later leg launches on these buffers again
+        o = outs[(a.warmup + a.steps - 1) % nd]
+        nh = int(o["c"][1].item())
+        dump_outputs(a.dump_outputs, "" if world == 1 else f"_rank{rank}", o["n"].cpu().numpy(),
+                     o["f"].cpu().numpy(), o["o"].cpu().numpy(),
+                     o["h"][:nh * HW].cpu().numpy().view(np.uint32).reshape(-1, HW),
+                     o["res"].cpu().numpy().view(np.uint32).reshape(-1, _lib.SP_RES_WORDS) if a.config == 4 else None)
     # per-kernel device time of every timed step: HIP events the library records on
     # its stream around k_widths and k_search (+ its overflow re-run) of each pass
     n_pt = min(a.steps, PASS_RING)             # the library keeps the newest PASS_RING passes per handle
@@ -1122,16 +1194,17 @@ def main():
     # per-pass HIP events of the launches the kernel times above belong to (the timed
     # ones, or the serialized roofline steps): their read sets' counters.  Every rank
     # measures its own; rank 0 reports them all.
-    ms_search, ms_widths = float(np.mean(s_ms)), float(np.mean(w_ms))
-    cset = {j: outs[j]["c"].cpu().numpy() for j in set(roof_sets)}
-    qs_launch = float(np.mean([cset[j][2] - cset[j][7] for j in roof_sets]))
-    qw_launch = float(np.mean([cset[j][7] for j in roof_sets]))
-    ach_search = qs_launch * BYTES_PER_QUERY / (ms_search / 1e3) / 1e9
-    ach_widths = qw_launch * BYTES_PER_QUERY / (ms_widths / 1e3) / 1e9
-    per_rank_roof = [(rank, ms_search, ach_search, rand_gbs)]
-    if world > 1:
-        per_rank_roof = [None] * world
-        dist.all_gather_object(per_rank_roof, (rank, ms_search, ach_search, rand_gbs))
+    if a.full:
+        ms_search, ms_widths = float(np.mean(s_ms)), float(np.mean(w_ms))
+        cset = {j: outs[j]["c"].cpu().numpy() for j in set(roof_sets)}
+        qs_launch = float(np.mean([cset[j][2] - cset[j][7] for j in roof_sets]))
+        qw_launch = float(np.mean([cset[j][7] for j in roof_sets]))
+        ach_search = qs_launch * BYTES_PER_QUERY / (ms_search / 1e3) / 1e9
+        ach_widths = qw_launch * BYTES_PER_QUERY / (ms_widths / 1e3) / 1e9
+        per_rank_roof = [(rank, ms_search, ach_search, rand_gbs)]
+        if world > 1:
+            per_rank_roof = [None] * world
+            dist.all_gather_object(per_rank_roof, (rank, ms_search, ach_search, rand_gbs))
 
     result = None
     if rank == 0:
@@ -1163,7 +1236,8 @@ def main():
                        "genome_bp": T, "reads_per_step": a.batch, "read_len": RL, "options": opt_str,
                        "parallelism": f"reads sharded over {world} GPU(s), index replicated",
                        "streams": S},
-            "roofline": {"bound": "hbm", "kernel": "k_search", "achieved": round(ach_search, 1), "peak": HBM_PEAK_GBS,
+            "roofline": None if not a.full else {   # evaluated under --full only: the probes and kernel times
+                         "bound": "hbm", "kernel": "k_search", "achieved": round(ach_search, 1), "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": round(ach_search / HBM_PEAK_GBS, 4),
                          "traffic": pk.get("k_search"),
                          "k_search_ms": round(ms_search, 3),
@@ -1211,11 +1285,14 @@ def main():
             "mapped_frac": round(mapped_all / reads_all, 4), "fallback_frac": round(fallback_all / reads_all, 4),
             "pops_per_read": round(pops / reads_local, 1),
         }
+        if not a.full:
+            del result["roofline"]
         if copies is not None:
             result["value_with_copies"] = copies
         if a.config == 4:
             result["seed_rank_queries_per_read"] = round(seed_queries / reads_local, 1)
-            result["roofline"]["splice_path_ms"] = round(splice_ms, 3)
+            if a.full:
+                result["roofline"]["splice_path_ms"] = round(splice_ms, 3)
             result["splice_path"] = splice
         if gather is not None:
             result["gather"] = gather

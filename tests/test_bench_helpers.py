@@ -61,6 +61,48 @@ def test_hits_in_read_order_and_digest():
     assert bench.batch_digest(o_n, o_f, h2) != d
 
 
+def test_dump_outputs_layout_independent_and_capped(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: two hit-buffer layouts of the same results give the same
+    files (float32 / float64, u32 words exact); over the byte budget the hit records are
+    those of a fixed sample of reads, in read order."""
+    o_n, o_f, o_h, g_n, g_f, g_o, g_h = _scrambled(np.random.default_rng(11), 600)
+    # the same results in another layout: each read's hits reversed in buffer order
+    g_o2 = (len(g_h) - g_o - g_n).astype(np.int64)
+    g_h2 = np.concatenate([g_h[g_o[r]:g_o[r] + g_n[r]] for r in np.argsort(-g_o, kind="stable")])
+    assert np.array_equal(bench.hits_in_read_order(g_n, g_o2, g_h2), o_h)
+    g_f = g_f | np.uint32(2) * (np.arange(600) % 7 == 0).astype(np.uint32)   # bit 1 is not part of the dump
+    o_off = np.concatenate([[0], np.cumsum(o_n.astype(np.int64))])
+    for cap_bytes in (bench.DUMP_HIT_BYTES, 72 * 100):
+        monkeypatch.setattr(bench, "DUMP_HIT_BYTES", cap_bytes)
+        a, b = str(tmp_path / f"a{cap_bytes}"), str(tmp_path / f"b{cap_bytes}")
+        bench.dump_outputs(a, "", g_n, g_f, g_o, g_h)
+        bench.dump_outputs(b, "", g_n, g_f, g_o2, g_h2)
+        got = {k: np.load(os.path.join(a, k + ".npy")) for k in ("n_aln", "fallback", "hit_reads", "hits")}
+        for k, v in got.items():
+            assert v.dtype == (np.float64 if k in ("hit_reads", "hits") else np.float32)
+            assert np.array_equal(v, np.load(os.path.join(b, k + ".npy"))), k
+        assert np.array_equal(got["n_aln"], o_n) and np.array_equal(got["fallback"], o_f & 1)
+        sel = got["hit_reads"].astype(np.int64)
+        assert np.all(np.diff(sel) > 0)
+        want = np.concatenate([o_h[o_off[r]:o_off[r + 1]] for r in sel])
+        assert np.array_equal(got["hits"], want.astype(np.float64))
+        if cap_bytes == 72 * 100:
+            assert 0 < len(sel) < 600 and len(got["hits"]) <= 100
+        else:
+            assert len(sel) == 600
+    # config 4's splice answers (one row per read of hit_reads) and config 5's 14-word records
+    res = np.arange(600 * 20, dtype=np.uint32).reshape(600, 20)
+    wide = np.concatenate([g_h, g_h[:, :5] ^ np.uint32(0xFFFFFFFF)], axis=1)
+    monkeypatch.setattr(bench, "DUMP_HIT_BYTES", 8 * (14 + 20) * 120)
+    c = str(tmp_path / "c")
+    bench.dump_outputs(c, "_rank1", g_n, g_f, g_o, wide, res)
+    sel = np.load(os.path.join(c, "hit_reads_rank1.npy")).astype(np.int64)
+    hits, sp = np.load(os.path.join(c, "hits_rank1.npy")), np.load(os.path.join(c, "splice_rank1.npy"))
+    assert 0 < len(sel) < 600 and len(hits) + len(sel) <= 120 and hits.shape[1] == 14
+    assert np.array_equal(sp, res[sel]) and len(hits) == int(o_n[sel].sum())
+    assert np.array_equal(hits[:, 9:], np.concatenate([o_h[o_off[r]:o_off[r + 1]] for r in sel])[:, :5] ^ 0xFFFFFFFF)
+
+
 def test_shard_pack_roundtrip_scrambled():
     """shard.pack puts each read's hits in read order whatever the kernel's layout."""
     from hsa_amd import shard

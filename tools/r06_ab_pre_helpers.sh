@@ -4,7 +4,7 @@
 set -e
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-B="--steps 20 --warmup 5 --dropin 0 --ref-sample 1600 --e2e-reads 0 --parity-sample 20000"
+B="--full --steps 20 --warmup 5 --dropin 0 --ref-sample 1600 --e2e-reads 0 --parity-sample 20000"
 for r in a b; do
   for v in pre new; do
     if [ $v = pre ]; then L=libhsa_gpu_r06pre.so; else L=libhsa_gpu.so; fi

@@ -7,7 +7,7 @@
 set -e
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-B="--steps 2 --warmup 1 --dropin 0 --ref-sample 1600 --parity-sample 4000"
+B="--full --steps 2 --warmup 1 --dropin 0 --ref-sample 1600 --parity-sample 4000"
 run() {   # name, env..., -- bench args
     local name=$1; shift
     env "$@" HSA_E2E_LOG=gpurun_out/e2e_$name.log timeout -k 10 500 python -u bench.py $B $EXTRA \
