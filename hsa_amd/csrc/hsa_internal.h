@@ -19,6 +19,30 @@ void hsa_set_error(const char *fmt, ...);
         }                                                                                   \
     } while (0)
 
+// The 16 slots of a search's counters (hsa_device_batch_t::d_counters; meanings and
+// values as include/hsa_gpu.h documents them: public ABI).  CTR_Q_*: the queue head a
+// pass takes its jobs from; the forward pass's and the caller-width pass's are internal.
+enum : uint32_t {
+    CTR_Q_MAIN = 0,        // the main pass's queue head
+    CTR_HITS = 1,          // hit records allocated
+    CTR_RANK = 2,          // rank queries the reference issues for these reads
+    CTR_SECTORS = 3,       // 64-byte rank sectors fetched
+    CTR_POPS = 4,          // gap_pop calls
+    CTR_ERRORS = 5,        // reads that pushed a score outside the regime's layout
+    CTR_Q_FWD = 6,         // the lazy forward pass's queue head
+    CTR_WIDTH_Q = 7,       // the width queries among CTR_RANK
+    CTR_OVF_MAIN = 8,      // reads that overflowed the main pass: the BIG pass's job count
+    CTR_Q_BIG = 9,         // the BIG pass's queue head
+    CTR_TRIE = 10,         // width steps answered by a root-trie load (k_widths passes)
+    CTR_Q_MG = 10,         // a caller-width main pass's queue head (no k_widths there)
+    CTR_UNFINISHED = 11,   // reads left unfinished by the last pass
+    CTR_OVF_BIG = 12,      // reads that overflowed the BIG pass: the HUGE pass's job count
+    CTR_FWD_Q_ALL = 13,    // width queries of every forward-strand row
+    CTR_FWD_Q_REF = 14,    // the part of CTR_FWD_Q_ALL the reference issues
+    CTR_Q_HUGE = 15,       // the HUGE pass's queue head
+    CTR_SLOTS = 16
+};
+
 // Per-launch scratch of the search kernel: grows, never shrinks.
 // Sized in entries (lanes x per-lane capacity): a launch indexes lane-interleaved
 // slots up to its own lanes * pcap, so a wide seed pass and a deep gapped pass share

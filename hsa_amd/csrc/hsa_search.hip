@@ -1,8 +1,9 @@
 // hsa_search.hip -- the 32-bit search API (include/hsa_gpu.h): host-array and
 // device-resident batches, direct bwt_match_gap calls, the splice seeds; the kernels
-// are in hsa_search_kernels.h.
-#include "hsa_search_kernels.h"
+// are in hsa_search_kernels.h, their planning and launching in hsa_search_launch.h.
+#include "hsa_search_launch.h"
 
+#include <memory>
 #include <vector>
 
 // ---------------------------------------------------------------- splice seeds
@@ -98,7 +99,7 @@ __global__ void __launch_bounds__(BLOCK) k_seed_prep(SeedArgs a)
     }
     const unsigned long long b0 = atomicAdd(a.count, 3ull);
     for (uint32_t tt = 0; tt < 3; ++tt) a.list[b0 + tt] = (int32_t)(r * 6u + 3u * s + tt);
-    atomicAdd(&a.ctr[7], (unsigned long long)q);
+    atomicAdd(&a.ctr[CTR_WIDTH_Q], (unsigned long long)q);
 }
 
 // ---------------------------------------------------------------- host side
@@ -118,12 +119,45 @@ extern "C" int hsa_diag_counters(unsigned long long *out, int reset)
     return 0;
 }
 #endif
+static size_t al(size_t x) { return (x + 255) / 256 * 256; }      // device regions start 256-byte aligned
+
 struct MgHost {
     const hsa_mg_job_t *mg;
     const int32_t *widths;
     size_t width_pairs;
     int32_t *widths_out;
 };
+
+// A host-array batch, and where its answers go (the C ABI's arrays).
+struct HostIn {
+    const hsa_job_t *jobs;
+    int n;
+    const uint8_t *codes;
+    size_t codes_len;
+    const MgHost *mh;              // caller widths (hsa_match_gap_batch), or null
+};
+
+struct HostOut {
+    int32_t *n_aln;
+    uint32_t *flags;
+    uint64_t *hit_off;
+    uint32_t **hits;               // malloc'ed: the caller frees it
+    hsa_stats_t *stats;
+};
+
+// Owners that let every early return (HSA_HIP) free what it holds.
+using HostHits = std::unique_ptr<uint32_t, void (*)(void *)>;   // hit records until they go to HostOut::hits
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+static HostHits alloc_hits(uint64_t records)
+{
+    HostHits h((uint32_t *)malloc((records + 1) * 36), free);
+    if (!h) hsa_set_error("host allocation of %llu hits failed", (unsigned long long)records);
+    return h;
+}
 
 // Checks of a caller-width batch; max_seed = the longest own width_seed.  A width_seed
 // with seed_len > len makes the reference read outside it: refused.
@@ -156,103 +190,138 @@ static int mg_limits(const hsa_job_t *jobs, const hsa_mg_job_t *mg, int n, const
     return 0;
 }
 
-// k_search_any over host arrays (hsa_search_any.h): reads longer than k_search holds,
-// or every read of a regime outside its layouts.  Same outputs as search_batch_impl.
-static long search_any_host(hsa_index_t *ix, const hsa_regime_t *regimes, int n_regimes, const hsa_job_t *jobs, int n,
-                            const uint8_t *codes, size_t codes_len, int32_t *n_aln, uint32_t *flags, uint64_t *hit_off,
-                            uint32_t **hits_out, hsa_stats_t *stats, const MgHost *mh)
+// A host batch on the device.  Inputs in ix->d_in: [regimes + bucket maps (1536) | jobs |
+// job list | codes | mg jobs | caller widths]; outputs in ix->d_out: [n_aln | flags |
+// hit_off | hits]; counters ix->d_ctr.  io.list, io.max_len and io.max_seed are the caller's.
+struct HostStage {
+    PassIO io;
+    int32_t *d_list;               // the job list slot (k_search's layout only)
+    int nb;                        // stack buckets (k_search's layout: stage_regimes)
+};
+
+// regimes: k_search's layout, the regimes staged with it (always copied: the call may
+// have moved d_in); codes padded by 1, a job list slot, room for 4 hits per read.
+// null: k_search_any's (the regimes are any_prepare's; a moved d_in invalidates the
+// fast path's staging); codes padded by 64, no list, room for 64 hits per read.
+static int stage_host(hsa_index *ix, const HostIn &in, const hsa_regime_t *regimes, int n_regimes, hipStream_t st,
+                      HostStage &H)
 {
-    HSA_HIP(hipSetDevice(ix->device));
-    hipStream_t st = ix->stream;
-    uint32_t max_len = 1, max_seed = 0;
-    for (int j = 0; j < n; ++j) {
-        if (jobs[j].len > max_len) max_len = jobs[j].len;
-        const bool own = mh ? mh->mg[j].seed == HSA_SEED_OWN : (int)jobs[j].len > jobs[j].seed_len;
-        if (own && (uint32_t)jobs[j].seed_len > max_seed) max_seed = (uint32_t)jobs[j].seed_len;
-    }
-    AnyBufs AB;
-    int rc = any_prepare(ix, regimes, n_regimes, (size_t)n, st, AB);
-    if (rc) return rc;
-    // inputs after the fast path's regime staging ([0, 1536) of d_in stays as it is)
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t o_jobs = 1536, o_codes = o_jobs + al((size_t)n * sizeof(hsa_job_t));
-    const size_t o_mg = o_codes + al(codes_len + 64), o_cw = o_mg + (mh ? al((size_t)n * sizeof(hsa_mg_job_t)) : 0);
+    const bool fast = regimes != nullptr;
+    const size_t n = (size_t)in.n;
+    const MgHost *mh = in.mh;
+    const size_t o_jobs = 1536, o_list = o_jobs + al(n * sizeof(hsa_job_t)), o_codes = o_list + (fast ? al(n * 4) : 0);
+    const size_t o_mg = o_codes + al(in.codes_len + (fast ? 1 : 64)), o_cw = o_mg + (mh ? al(n * sizeof(hsa_mg_job_t)) : 0);
     const size_t cw_bytes = mh ? mh->width_pairs * 8 : 0;
     void *before = ix->d_in;
-    if ((rc = hsa_grow(&ix->d_in, &ix->d_in_cap, o_cw + cw_bytes + 256))) return rc;
-    if (before != ix->d_in) ix->staged_valid = 0;       // the regime staging went with the old buffer
+    int rc = hsa_grow(&ix->d_in, &ix->d_in_cap, o_cw + cw_bytes + 256);
+    if (rc) return rc;
     char *din = (char *)ix->d_in;
-    HSA_HIP(hipMemcpyAsync(din + o_jobs, jobs, sizeof(hsa_job_t) * n, hipMemcpyHostToDevice, st));
-    HSA_HIP(hipMemcpyAsync(din + o_codes, codes, codes_len, hipMemcpyHostToDevice, st));
-    MgPass mgp{nullptr, nullptr};
+    H.nb = 0;
+    if (fast && (rc = stage_regimes(ix, regimes, n_regimes, H.nb, st, true))) return rc;
+    if (!fast && before != ix->d_in) ix->staged_valid = 0;
+    HSA_HIP(hipMemcpyAsync(din + o_jobs, in.jobs, sizeof(hsa_job_t) * n, hipMemcpyHostToDevice, st));
+    HSA_HIP(hipMemcpyAsync(din + o_codes, in.codes, in.codes_len, hipMemcpyHostToDevice, st));
     if (mh) {
         HSA_HIP(hipMemcpyAsync(din + o_mg, mh->mg, sizeof(hsa_mg_job_t) * n, hipMemcpyHostToDevice, st));
         HSA_HIP(hipMemcpyAsync(din + o_cw, mh->widths, cw_bytes, hipMemcpyHostToDevice, st));
-        mgp = MgPass{(const hsa_mg_job_t *)(din + o_mg), (int32_t *)(din + o_cw)};
     }
-    const uint64_t hit_cap = (uint64_t)n * 64 + 65536;
-    const size_t o_fl = al((size_t)n * 4), o_ho = o_fl + al((size_t)n * 4), o_hits = o_ho + al((size_t)n * 8);
+    H.d_list = (int32_t *)(din + o_list);
+    const uint64_t hit_cap = fast ? (uint64_t)n * 4 + 4096 : (uint64_t)n * 64 + 65536;
+    const size_t o_fl = al(n * 4), o_ho = o_fl + al(n * 4), o_hits = o_ho + al(n * 8);
     if ((rc = hsa_grow(&ix->d_out, &ix->d_out_cap, o_hits + hit_cap * 36 + 256))) return rc;
     char *dout = (char *)ix->d_out;
-    unsigned long long *d_ctr = (unsigned long long *)ix->d_ctr;
-    HSA_HIP(hipMemsetAsync(d_ctr, 0, 16 * sizeof(unsigned long long), st));
-    HSA_HIP(hipEventRecord(ix->ev0, st));
-    const hsa_job_t *dj = (const hsa_job_t *)(din + o_jobs);
-    const uint8_t *dc = (const uint8_t *)(din + o_codes);
-    int32_t *d_n = (int32_t *)dout;
-    uint32_t *d_fl = (uint32_t *)(dout + o_fl);
-    uint64_t *d_ho = (uint64_t *)(dout + o_ho);
-    uint32_t *d_hits = (uint32_t *)(dout + o_hits);
-    if ((rc = any_pass<uint32_t>(ix, AB, regimes, n_regimes, dj, nullptr, nullptr, n, (size_t)n, max_len, max_seed, dc,
-                                 mh ? &mgp : nullptr, d_n, d_fl, d_ho, d_hits, hit_cap, d_ctr, AB.cnt + 2, AB.l_ovf,
-                                 AB.cnt + 3, false, st)) ||
-        (rc = any_pass<uint32_t>(ix, AB, regimes, n_regimes, dj, AB.l_ovf, AB.cnt + 3, 0, (size_t)n, max_len, max_seed,
-                                 dc, mh ? &mgp : nullptr, d_n, d_fl, d_ho, d_hits, hit_cap, d_ctr, AB.cnt + 4, nullptr,
-                                 nullptr, true, st)))
-        return rc;
-    HSA_HIP(hipEventRecord(ix->ev1, st));
-    unsigned long long ctr[16];
-    HSA_HIP(hipMemcpyAsync(ctr, d_ctr, sizeof ctr, hipMemcpyDeviceToHost, st));
-    HSA_HIP(hipMemcpyAsync(n_aln, d_n, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    HSA_HIP(hipMemcpyAsync(flags, d_fl, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    HSA_HIP(hipMemcpyAsync(hit_off, d_ho, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    H.io = PassIO{.jobs = (const hsa_job_t *)(din + o_jobs), .list = nullptr, .n = in.n,
+                  .codes = (const uint8_t *)(din + o_codes), .n_aln = (int32_t *)dout, .flags = (uint32_t *)(dout + o_fl),
+                  .hit_off = (uint64_t *)(dout + o_ho), .hits = (uint32_t *)(dout + o_hits), .hit_cap = hit_cap,
+                  .ctr = (unsigned long long *)ix->d_ctr, .max_len = 0, .max_seed = 0,
+                  .mg = mh ? MgPass{(const hsa_mg_job_t *)(din + o_mg), (int32_t *)(din + o_cw)} : MgPass{}};
+    return 0;
+}
+
+// The counters and the per-job arrays of a pass (n entries each) to the host, complete on return.
+static int copy_back(const PassIO &io, int n, const HostOut &to, unsigned long long *ctr, hipStream_t st)
+{
+    HSA_HIP(hipMemcpyAsync(ctr, io.ctr, CTR_SLOTS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HSA_HIP(hipMemcpyAsync(to.n_aln, io.n_aln, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HSA_HIP(hipMemcpyAsync(to.flags, io.flags, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HSA_HIP(hipMemcpyAsync(to.hit_off, io.hit_off, (size_t)n * 8, hipMemcpyDeviceToHost, st));
     HSA_HIP(hipStreamSynchronize(st));
-    if (ctr[5]) { hsa_set_error("%llu reads pushed a score past the regime's n_stacks", ctr[5]); return HSA_E_ARG; }
-    if (ctr[11]) { hsa_set_error("%llu reads exceed the large-pass capacity", ctr[11]); return HSA_E_ARG; }
+    return 0;
+}
+
+// width_back of every call after its search (k_widths_export wrote them in place)
+static int export_widths(const HostIn &in, const HostStage &H)
+{
+    const MgHost *mh = in.mh;
+    std::vector<int32_t> cw(2 * mh->width_pairs + 2);
+    HSA_HIP(hipMemcpy(cw.data(), H.io.mg.d_cw, mh->width_pairs * 8, hipMemcpyDeviceToHost));
+    for (int j = 0; j < in.n; ++j)
+        memcpy(mh->widths_out + 2 * mh->mg[j].wb_off, cw.data() + 2 * mh->mg[j].wb_off, 8 * ((size_t)in.jobs[j].len + 1));
+    return 0;
+}
+
+// main: the batch's first pass (a re-run round adds to the work and the kernel time only)
+static void add_stats(hsa_stats_t *stats, const unsigned long long *ctr, float ms, bool main)
+{
+    if (!stats) return;
+    stats->rank_queries += ctr[CTR_RANK]; stats->blocks_loaded += ctr[CTR_SECTORS]; stats->pops += ctr[CTR_POPS];
+    stats->kernel_ms += ms;
+    if (main) { stats->main_kernel_ms += ms; stats->main_launches += 1; }
+}
+
+// k_search_any over host arrays (hsa_search_any.h): reads longer than k_search holds,
+// or every read of a regime outside its layouts.  Same outputs as search_batch_impl.
+static long search_any_host(hsa_index_t *ix, const hsa_regime_t *regimes, int n_regimes, const HostIn &in,
+                            const HostOut &out)
+{
+    HSA_HIP(hipSetDevice(ix->device));
+    hipStream_t st = ix->stream;
+    const hsa_job_t *jobs = in.jobs;
+    uint32_t max_len = 1, max_seed = 0;
+    for (int j = 0; j < in.n; ++j) {
+        if (jobs[j].len > max_len) max_len = jobs[j].len;
+        const bool own = in.mh ? in.mh->mg[j].seed == HSA_SEED_OWN : (int)jobs[j].len > jobs[j].seed_len;
+        if (own && (uint32_t)jobs[j].seed_len > max_seed) max_seed = (uint32_t)jobs[j].seed_len;
+    }
+    AnyBufs AB;
+    int rc = any_prepare(ix, regimes, n_regimes, (size_t)in.n, st, AB);
+    if (rc) return rc;
+    HostStage H;
+    if ((rc = stage_host(ix, in, nullptr, 0, st, H))) return rc;
+    H.io.max_len = (int)max_len; H.io.max_seed = (int)max_seed;
+    HSA_HIP(hipMemsetAsync(H.io.ctr, 0, CTR_SLOTS * sizeof(unsigned long long), st));
+    HSA_HIP(hipEventRecord(ix->ev0, st));
+    if ((rc = any_passes<uint32_t>(ix, AB, H.io, nullptr, st))) return rc;
+    HSA_HIP(hipEventRecord(ix->ev1, st));
+    unsigned long long ctr[CTR_SLOTS];
+    if ((rc = copy_back(H.io, in.n, out, ctr, st))) return rc;
+    if (ctr[CTR_ERRORS]) { hsa_set_error("%llu reads pushed a score past the regime's n_stacks", ctr[CTR_ERRORS]); return HSA_E_ARG; }
+    if (ctr[CTR_UNFINISHED]) { hsa_set_error("%llu reads exceed the large-pass capacity", ctr[CTR_UNFINISHED]); return HSA_E_ARG; }
     float ms = 0;
     HSA_HIP(hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
-    const uint64_t total = ctr[1] < hit_cap ? ctr[1] : hit_cap;
-    uint32_t *h = (uint32_t *)malloc((total + 1) * 36);
-    if (!h) { hsa_set_error("host allocation of %llu hits failed", (unsigned long long)total); return HSA_E_MEM; }
-    if (total) HSA_HIP(hipMemcpy(h, d_hits, total * 36, hipMemcpyDeviceToHost));
-    if (mh) {
-        int32_t *cw = (int32_t *)malloc(cw_bytes + 8);
-        HSA_HIP(hipMemcpy(cw, din + o_cw, cw_bytes, hipMemcpyDeviceToHost));
-        for (int j = 0; j < n; ++j)
-            memcpy(mh->widths_out + 2 * mh->mg[j].wb_off, cw + 2 * mh->mg[j].wb_off, 8 * ((size_t)jobs[j].len + 1));
-        free(cw);
-    }
-    if (stats) {
-        stats->rank_queries += ctr[2]; stats->blocks_loaded += ctr[3]; stats->pops += ctr[4];
-        stats->kernel_ms += ms; stats->main_kernel_ms += ms; stats->main_launches += 1;
-    }
-    *hits_out = h;
+    const uint64_t total = ctr[CTR_HITS] < H.io.hit_cap ? ctr[CTR_HITS] : H.io.hit_cap;
+    HostHits h = alloc_hits(total);
+    if (!h) return HSA_E_MEM;
+    if (total) HSA_HIP(hipMemcpy(h.get(), H.io.hits, total * 36, hipMemcpyDeviceToHost));
+    if (in.mh && (rc = export_widths(in, H))) return rc;
+    add_stats(out.stats, ctr, ms, true);
+    *out.hits = h.release();
     return (long)total;
 }
 
+static long search_batch_impl(hsa_index_t *ix, const hsa_regime_t *regimes, int n_regimes, const HostIn &in,
+                              const HostOut &out);
+
 // A batch with reads (or a regime) k_search cannot hold: the reads it can hold through
 // search_batch_impl, the others through k_search_any; outputs merged in job order.
-static long search_batch_impl(hsa_index_t *ix, const hsa_regime_t *regimes, int n_regimes, const hsa_job_t *jobs,
-                              int n_jobs, const uint8_t *codes, size_t codes_len, int32_t *n_aln, uint32_t *flags,
-                              uint64_t *hit_off, uint32_t **hits_out, hsa_stats_t *stats, const MgHost *mh);
-
-static long search_split(hsa_index_t *ix, const hsa_regime_t *regimes, int n_regimes, const hsa_job_t *jobs, int n,
-                         const uint8_t *codes, size_t codes_len, int32_t *n_aln, uint32_t *flags, uint64_t *hit_off,
-                         uint32_t **hits_out, hsa_stats_t *stats, const MgHost *mh, bool fast_rg)
+static long search_split(hsa_index_t *ix, const hsa_regime_t *regimes, int n_regimes, const HostIn &in, const HostOut &out,
+                         bool fast_rg)
 {
+    const MgHost *mh = in.mh;
+    hsa_stats_t *stats = out.stats;
     std::vector<int> part[2];                        // 0: k_search, 1: k_search_any
-    for (int j = 0; j < n; ++j) part[fast_rg && jobs[j].len <= FAST_MAX_LEN ? 0 : 1].push_back(j);
-    uint32_t *hs[2] = {nullptr, nullptr};
+    for (int j = 0; j < in.n; ++j) part[fast_rg && in.jobs[j].len <= FAST_MAX_LEN ? 0 : 1].push_back(j);
+    HostHits hs[2] = {HostHits(nullptr, free), HostHits(nullptr, free)};
     long tot[2] = {0, 0};
     if (stats) memset(stats, 0, sizeof *stats);
     for (int k = 0; k < 2; ++k) {
@@ -261,24 +330,25 @@ static long search_split(hsa_index_t *ix, const hsa_regime_t *regimes, int n_reg
         std::vector<hsa_job_t> pj(m);
         std::vector<hsa_mg_job_t> pm(mh ? m : 0);
         for (int q = 0; q < m; ++q) {
-            pj[q] = jobs[part[k][q]];
+            pj[q] = in.jobs[part[k][q]];
             if (mh) pm[q] = mh->mg[part[k][q]];
         }
         const MgHost pmh = mh ? MgHost{pm.data(), mh->widths, mh->width_pairs, mh->widths_out} : MgHost{};
         std::vector<int32_t> na(m);
         std::vector<uint32_t> fl(m);
         std::vector<uint64_t> ho(m);
-        hsa_stats_t ps;
-        memset(&ps, 0, sizeof ps);
-        const long t = k == 0 ? search_batch_impl(ix, regimes, n_regimes, pj.data(), m, codes, codes_len, na.data(), fl.data(),
-                                                  ho.data(), &hs[k], &ps, mh ? &pmh : nullptr)
-                              : search_any_host(ix, regimes, n_regimes, pj.data(), m, codes, codes_len, na.data(),
-                                                fl.data(), ho.data(), &hs[k], &ps, mh ? &pmh : nullptr);
-        if (t < 0) { free(hs[0]); free(hs[1]); return t; }
+        hsa_stats_t ps{};
+        uint32_t *ph = nullptr;
+        const HostIn pin{pj.data(), m, in.codes, in.codes_len, mh ? &pmh : nullptr};
+        const HostOut pout{na.data(), fl.data(), ho.data(), &ph, &ps};
+        const long t = k == 0 ? search_batch_impl(ix, regimes, n_regimes, pin, pout)
+                              : search_any_host(ix, regimes, n_regimes, pin, pout);
+        hs[k].reset(ph);
+        if (t < 0) return t;
         tot[k] = t;
         for (int q = 0; q < m; ++q) {
             const int j = part[k][q];
-            n_aln[j] = na[q]; flags[j] = fl[q]; hit_off[j] = ho[q] + (k ? (uint64_t)tot[0] : 0);
+            out.n_aln[j] = na[q]; out.flags[j] = fl[q]; out.hit_off[j] = ho[q] + (k ? (uint64_t)tot[0] : 0);
         }
         if (stats) {
             stats->rank_queries += ps.rank_queries; stats->blocks_loaded += ps.blocks_loaded; stats->pops += ps.pops;
@@ -286,19 +356,23 @@ static long search_split(hsa_index_t *ix, const hsa_regime_t *regimes, int n_reg
             stats->main_kernel_ms += ps.main_kernel_ms; stats->main_launches += ps.main_launches;
         }
     }
-    uint32_t *h = (uint32_t *)malloc(((size_t)tot[0] + (size_t)tot[1] + 1) * 36);
-    if (tot[0]) memcpy(h, hs[0], (size_t)tot[0] * 36);
-    if (tot[1]) memcpy(h + (size_t)tot[0] * 9, hs[1], (size_t)tot[1] * 36);
-    free(hs[0]); free(hs[1]);
-    *hits_out = h;
+    HostHits h = alloc_hits((uint64_t)tot[0] + (uint64_t)tot[1]);
+    if (!h) return HSA_E_MEM;
+    if (tot[0]) memcpy(h.get(), hs[0].get(), (size_t)tot[0] * 36);
+    if (tot[1]) memcpy(h.get() + (size_t)tot[0] * 9, hs[1].get(), (size_t)tot[1] * 36);
+    *out.hits = h.release();
     return tot[0] + tot[1];
 }
 
-static long search_batch_impl(hsa_index_t *ix, const hsa_regime_t *regimes, int n_regimes, const hsa_job_t *jobs,
-                              int n_jobs, const uint8_t *codes, size_t codes_len, int32_t *n_aln, uint32_t *flags,
-                              uint64_t *hit_off, uint32_t **hits_out, hsa_stats_t *stats, const MgHost *mh)
+static long search_batch_impl(hsa_index_t *ix, const hsa_regime_t *regimes, int n_regimes, const HostIn &in,
+                              const HostOut &out)
 {
-    *hits_out = nullptr;
+    const hsa_job_t *jobs = in.jobs;
+    const int n_jobs = in.n;
+    const size_t codes_len = in.codes_len;
+    const MgHost *mh = in.mh;
+    hsa_stats_t *stats = out.stats;
+    *out.hits = nullptr;
     if (n_regimes < 1 || n_regimes > 2) { hsa_set_error("1 or 2 regimes"); return HSA_E_ARG; }
     if (int rc0 = hsa_need32(ix)) return rc0;
     int rc = check_regimes(regimes, n_regimes);
@@ -314,155 +388,87 @@ static long search_batch_impl(hsa_index_t *ix, const hsa_regime_t *regimes, int 
                           jobs[j].len, codes_len);
             return HSA_E_ARG;
         }
-    {
-        const bool fast_rg = fast_regimes(regimes, n_regimes);
-        bool all_fit = fast_rg;
-        for (int j = 0; j < n_jobs && all_fit; ++j) all_fit = jobs[j].len <= FAST_MAX_LEN;
-        if (!all_fit)
-            return search_split(ix, regimes, n_regimes, jobs, n_jobs, codes, codes_len, n_aln, flags, hit_off, hits_out,
-                                stats, mh, fast_rg);
-    }
-    HSA_HIP(hipSetDevice(ix->device));
+    const bool fast_rg = fast_regimes(regimes, n_regimes);
+    bool all_fit = fast_rg;
+    for (int j = 0; j < n_jobs && all_fit; ++j) all_fit = jobs[j].len <= FAST_MAX_LEN;
+    if (!all_fit) return search_split(ix, regimes, n_regimes, in, out, fast_rg);
     hipStream_t st = ix->stream;
     if (stats) memset(stats, 0, sizeof *stats);
-    if (n_jobs == 0) { *hits_out = (uint32_t *)calloc(9, 4); return 0; }
+    if (n_jobs == 0) { *out.hits = (uint32_t *)calloc(9, 4); return 0; }
     static const bool verbose = getenv("HSA_VERBOSE") != nullptr;
     const auto now = []() { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec + 1e-9 * t.tv_nsec; };
     const double tv0 = verbose ? now() : 0.0;
 
-    // device staging: regimes+bmap | jobs | list | codes [| mg jobs | caller widths]
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t o_reg = 0, o_jobs = 1536, o_list = o_jobs + al((size_t)n_jobs * sizeof(hsa_job_t));
-    const size_t o_codes = o_list + al((size_t)n_jobs * 4);
-    const size_t o_mg = o_codes + al(codes_len + 1);
-    const size_t o_cw = o_mg + (mh ? al((size_t)n_jobs * sizeof(hsa_mg_job_t)) : 0);
-    const size_t cw_bytes = mh ? mh->width_pairs * 8 : 0;
-    if ((rc = hsa_grow(&ix->d_in, &ix->d_in_cap, o_cw + cw_bytes + 256))) return rc;
-    char *din = (char *)ix->d_in;
-    int nb = 0;
-    if ((rc = stage_regimes(ix, regimes, n_regimes, din + o_reg, nb, st, true))) return rc;
-    const hsa_regime_t *d_reg = (const hsa_regime_t *)(din + o_reg);
-    const uint8_t *d_bmap = (const uint8_t *)(din + o_reg + 256);
-    HSA_HIP(hipMemcpyAsync(din + o_jobs, jobs, sizeof(hsa_job_t) * n_jobs, hipMemcpyHostToDevice, st));
-    HSA_HIP(hipMemcpyAsync(din + o_codes, codes, codes_len, hipMemcpyHostToDevice, st));
-    MgPass mgp{nullptr, nullptr};
-    if (mh) {
-        HSA_HIP(hipMemcpyAsync(din + o_mg, mh->mg, sizeof(hsa_mg_job_t) * n_jobs, hipMemcpyHostToDevice, st));
-        HSA_HIP(hipMemcpyAsync(din + o_cw, mh->widths, cw_bytes, hipMemcpyHostToDevice, st));
-        mgp = MgPass{(const hsa_mg_job_t *)(din + o_mg), (int32_t *)(din + o_cw)};
-    }
-    const MgPass *mgpp = mh ? &mgp : nullptr;
-    // outputs: n_aln | flags | hit_off | hits
-    uint64_t hit_cap = (uint64_t)n_jobs * 4 + 4096;
-    const size_t o_fl = ((size_t)n_jobs * 4 + 255) / 256 * 256;
-    const size_t o_ho = o_fl + ((size_t)n_jobs * 4 + 255) / 256 * 256;
-    const size_t o_hits = o_ho + ((size_t)n_jobs * 8 + 255) / 256 * 256;
-    if ((rc = hsa_grow(&ix->d_out, &ix->d_out_cap, o_hits + hit_cap * 36 + 256))) return rc;
-    char *dout = (char *)ix->d_out;
-    int32_t *d_n = (int32_t *)dout;
-    uint32_t *d_fl = (uint32_t *)(dout + o_fl);
-    uint64_t *d_ho = (uint64_t *)(dout + o_ho);
-    uint32_t *d_hits = (uint32_t *)(dout + o_hits);
-    unsigned long long *d_ctr = (unsigned long long *)ix->d_ctr;
-
+    HostStage H;
+    if ((rc = stage_host(ix, in, regimes, n_regimes, st, H))) return rc;
+    H.io.max_len = max_len; H.io.max_seed = max_seed;
     LaunchPlan P;
-    const bool gaps = any_gaps(regimes, n_regimes);
-    const bool wide = need_wide(regimes, n_regimes);
-    bool nib_ok = !mgpp && nib_exact(regimes, n_regimes);
-    for (int j = 0; j < n_jobs && nib_ok; ++j) nib_ok = jobs[j].max_diff <= 6;
-    if ((rc = plan_launch(ix, n_jobs, max_len, max_seed, nb, gaps, wide, PASS_MAIN, P, 0, 16, nib_ok))) return rc;
+    RegimePlan R = regime_plan(regimes, n_regimes);
+    R.nb = H.nb;
+    R.nib_ok = R.nib_ok && !mh;
+    for (int j = 0; j < n_jobs && R.nib_ok; ++j) R.nib_ok = jobs[j].max_diff <= 6;
+    if ((rc = plan_launch(ix, n_jobs, max_len, max_seed, R, PASS_MAIN, P))) return rc;
     HSA_HIP(hipEventRecord(ix->ev0, st));
-    if ((rc = launch_pass(ix, P, ix->main, d_reg, d_bmap, (const hsa_job_t *)(din + o_jobs), nullptr, n_jobs,
-                          max_len, max_seed, (const uint8_t *)(din + o_codes), d_n, d_fl, d_ho, d_hits, hit_cap, d_ctr, st,
-                          nullptr, nullptr, 0, mgpp)))
-        return rc;
+    if ((rc = launch_pass(ix, P, ix->main, H.io, PassLink{}, st))) return rc;
     HSA_HIP(hipEventRecord(ix->ev1, st));
-    unsigned long long ctr[8];
-    HSA_HIP(hipMemcpyAsync(ctr, d_ctr, sizeof ctr, hipMemcpyDeviceToHost, st));
-    HSA_HIP(hipMemcpyAsync(n_aln, d_n, (size_t)n_jobs * 4, hipMemcpyDeviceToHost, st));
-    HSA_HIP(hipMemcpyAsync(flags, d_fl, (size_t)n_jobs * 4, hipMemcpyDeviceToHost, st));
-    HSA_HIP(hipMemcpyAsync(hit_off, d_ho, (size_t)n_jobs * 8, hipMemcpyDeviceToHost, st));
-    HSA_HIP(hipStreamSynchronize(st));
-    if (ctr[5]) { hsa_set_error("%llu reads exceed the regime's max_diff bound", ctr[5]); return HSA_E_ARG; }
+    unsigned long long ctr[CTR_SLOTS];
+    if ((rc = copy_back(H.io, n_jobs, out, ctr, st))) return rc;
+    if (ctr[CTR_ERRORS]) { hsa_set_error("%llu reads exceed the regime's max_diff bound", ctr[CTR_ERRORS]); return HSA_E_ARG; }
     float ms = 0;
     HSA_HIP(hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
-    uint64_t total = ctr[1] < hit_cap ? ctr[1] : hit_cap;
+    uint64_t total = ctr[CTR_HITS] < H.io.hit_cap ? ctr[CTR_HITS] : H.io.hit_cap;
     const double tv1 = verbose ? now() : 0.0;
-    uint32_t *h = (uint32_t *)malloc((total + 1) * 36);
-    if (total) HSA_HIP(hipMemcpy(h, d_hits, total * 36, hipMemcpyDeviceToHost));
+    HostHits h = alloc_hits(total);
+    if (!h) return HSA_E_MEM;
+    if (total) HSA_HIP(hipMemcpy(h.get(), H.io.hits, total * 36, hipMemcpyDeviceToHost));
     if (verbose)
         fprintf(stderr, "[hsa] search of %d reads: copies in + kernels + result arrays out %.1f ms (kernels %.1f ms), "
                         "hits out %.1f ms\n", n_jobs, 1e3 * (tv1 - tv0), ms, 1e3 * (now() - tv1));
-    if (stats) {
-        stats->rank_queries += ctr[2]; stats->blocks_loaded += ctr[3]; stats->pops += ctr[4];
-        stats->kernel_ms += ms; stats->main_kernel_ms += ms; stats->main_launches += 1;
-    }
+    add_stats(stats, ctr, ms, true);
 
-    // overflowed reads: re-run with large per-read capacity (never a CPU path)
+    // overflowed reads: re-run with large per-read capacity (never a CPU path), each round
+    // into hit buffers of its own
+    std::vector<int32_t> list, n2;
+    std::vector<uint32_t> f2;
+    std::vector<uint64_t> o2;
     for (int round = 0; round < 4; ++round) {
-        int32_t *list = (int32_t *)malloc(sizeof(int32_t) * n_jobs);
-        int n_over = 0;
-        for (int j = 0; j < n_jobs; ++j) if (flags[j] & HSA_F_OVERFLOW) list[n_over++] = j;
-        if (n_over == 0) { free(list); break; }
+        list.clear();
+        for (int j = 0; j < n_jobs; ++j) if (out.flags[j] & HSA_F_OVERFLOW) list.push_back(j);
+        const int n_over = (int)list.size();
+        if (n_over == 0) break;
+        n2.resize(n_jobs); f2.resize(n_jobs); o2.resize(n_jobs);
         if (stats) stats->overflow_reruns += n_over;
         LaunchPlan B;
-        int max_entries = 0;
-        for (int r = 0; r < n_regimes; ++r) max_entries = regimes[r].max_entries > max_entries ? regimes[r].max_entries : max_entries;
         const int mode = round == 0 ? PASS_BIG : PASS_HUGE;
-        if ((rc = plan_launch(ix, n_over, max_len, max_seed, nb, gaps, wide, mode, B, max_entries, 16, nib_ok))) {
-            free(list); free(h); return rc;
-        }
-        uint64_t cap2 = (uint64_t)n_over * 256 * (round + 1) + 65536;
-        void *d2 = nullptr;
-        size_t o2_fl = ((size_t)n_jobs * 4 + 255) / 256 * 256;
-        size_t o2_ho = o2_fl * 2, o2_hits = o2_ho + ((size_t)n_jobs * 8 + 255) / 256 * 256;
-        HSA_HIP(hipMalloc(&d2, o2_hits + cap2 * 36));
-        HSA_HIP(hipMemcpyAsync(din + o_list, list, sizeof(int32_t) * n_over, hipMemcpyHostToDevice, st));
-        char *c2 = (char *)d2;
+        if ((rc = plan_launch(ix, n_over, max_len, max_seed, R, mode, B))) return rc;
+        const uint64_t cap2 = (uint64_t)n_over * 256 * (round + 1) + 65536;
+        const size_t o2_fl = al((size_t)n_jobs * 4), o2_ho = o2_fl * 2, o2_hits = o2_ho + al((size_t)n_jobs * 8);
+        DevBuf d2;
+        HSA_HIP(hipMalloc(&d2.p, o2_hits + cap2 * 36));
+        HSA_HIP(hipMemcpyAsync(H.d_list, list.data(), sizeof(int32_t) * n_over, hipMemcpyHostToDevice, st));
+        char *c2 = (char *)d2.p;
+        PassIO io2 = H.io;
+        io2.list = H.d_list; io2.n = n_over;
+        io2.n_aln = (int32_t *)c2; io2.flags = (uint32_t *)(c2 + o2_fl); io2.hit_off = (uint64_t *)(c2 + o2_ho);
+        io2.hits = (uint32_t *)(c2 + o2_hits); io2.hit_cap = cap2;
         HSA_HIP(hipEventRecord(ix->ev0, st));
-        if ((rc = launch_pass(ix, B, mode == PASS_BIG ? ix->big : ix->huge, d_reg, d_bmap, (const hsa_job_t *)(din + o_jobs),
-                              (const int32_t *)(din + o_list), n_over, max_len, max_seed,
-                              (const uint8_t *)(din + o_codes), (int32_t *)c2,
-                              (uint32_t *)(c2 + o2_fl), (uint64_t *)(c2 + o2_ho), (uint32_t *)(c2 + o2_hits), cap2,
-                              d_ctr, st, nullptr, nullptr, 0, mgpp))) {
-            free(list); free(h); (void)hipFree(d2); return rc;
-        }
+        if ((rc = launch_pass(ix, B, mode == PASS_BIG ? ix->big : ix->huge, io2, PassLink{}, st))) return rc;
         HSA_HIP(hipEventRecord(ix->ev1, st));
-        int32_t *n2 = (int32_t *)malloc((size_t)n_jobs * 4);
-        uint32_t *f2 = (uint32_t *)malloc((size_t)n_jobs * 4);
-        uint64_t *o2 = (uint64_t *)malloc((size_t)n_jobs * 8);
-        HSA_HIP(hipMemcpyAsync(ctr, d_ctr, sizeof ctr, hipMemcpyDeviceToHost, st));
-        HSA_HIP(hipMemcpyAsync(n2, c2, (size_t)n_jobs * 4, hipMemcpyDeviceToHost, st));
-        HSA_HIP(hipMemcpyAsync(f2, c2 + o2_fl, (size_t)n_jobs * 4, hipMemcpyDeviceToHost, st));
-        HSA_HIP(hipMemcpyAsync(o2, c2 + o2_ho, (size_t)n_jobs * 8, hipMemcpyDeviceToHost, st));
-        HSA_HIP(hipStreamSynchronize(st));
+        if ((rc = copy_back(io2, n_jobs, HostOut{n2.data(), f2.data(), o2.data(), nullptr, nullptr}, ctr, st))) return rc;
         HSA_HIP(hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
-        uint64_t t2 = ctr[1] < cap2 ? ctr[1] : cap2;
-        h = (uint32_t *)realloc(h, (total + t2 + 1) * 36);
-        if (t2) HSA_HIP(hipMemcpy(h + total * 9, c2 + o2_hits, t2 * 36, hipMemcpyDeviceToHost));
-        for (int q = 0; q < n_over; ++q) {
-            int j = list[q];
-            n_aln[j] = n2[j]; flags[j] = f2[j]; hit_off[j] = o2[j] + total;
-        }
+        const uint64_t t2 = ctr[CTR_HITS] < cap2 ? ctr[CTR_HITS] : cap2;
+        uint32_t *grown = (uint32_t *)realloc(h.get(), (total + t2 + 1) * 36);
+        if (!grown) { hsa_set_error("host allocation of %llu hits failed", (unsigned long long)(total + t2)); return HSA_E_MEM; }
+        (void)h.release(); h.reset(grown);
+        if (t2) HSA_HIP(hipMemcpy(h.get() + total * 9, io2.hits, t2 * 36, hipMemcpyDeviceToHost));
+        for (const int j : list) { out.n_aln[j] = n2[j]; out.flags[j] = f2[j]; out.hit_off[j] = o2[j] + total; }
         total += t2;
-        if (stats) {
-            stats->rank_queries += ctr[2]; stats->blocks_loaded += ctr[3]; stats->pops += ctr[4];
-            stats->kernel_ms += ms;
-        }
-        free(n2); free(f2); free(o2); free(list);
-        (void)hipFree(d2);
+        add_stats(stats, ctr, ms, false);
     }
     for (int j = 0; j < n_jobs; ++j)
-        if (flags[j] & HSA_F_OVERFLOW) { hsa_set_error("read %d exceeds the large-pass capacity", j); free(h); return HSA_E_ARG; }
-    if (mh) {
-        // width_back of every call after its search (k_widths_export wrote them in place)
-        int32_t *cw = (int32_t *)malloc(cw_bytes + 8);
-        HSA_HIP(hipMemcpy(cw, din + o_cw, cw_bytes, hipMemcpyDeviceToHost));
-        for (int j = 0; j < n_jobs; ++j)
-            memcpy(mh->widths_out + 2 * mh->mg[j].wb_off, cw + 2 * mh->mg[j].wb_off, 8 * ((size_t)jobs[j].len + 1));
-        free(cw);
-    }
-    *hits_out = h;
+        if (out.flags[j] & HSA_F_OVERFLOW) { hsa_set_error("read %d exceeds the large-pass capacity", j); return HSA_E_ARG; }
+    if (mh && (rc = export_widths(in, H))) return rc;
+    *out.hits = h.release();
     return (long)total;
 }
 
@@ -470,8 +476,8 @@ extern "C" long hsa_search_batch(hsa_index_t *ix, const hsa_regime_t *regimes, i
                                  int n_jobs, const uint8_t *codes, size_t codes_len, int32_t *n_aln, uint32_t *flags,
                                  uint64_t *hit_off, uint32_t **hits_out, hsa_stats_t *stats)
 {
-    return search_batch_impl(ix, regimes, n_regimes, jobs, n_jobs, codes, codes_len, n_aln, flags, hit_off, hits_out,
-                             stats, nullptr);
+    return search_batch_impl(ix, regimes, n_regimes, HostIn{jobs, n_jobs, codes, codes_len, nullptr},
+                             HostOut{n_aln, flags, hit_off, hits_out, stats});
 }
 
 extern "C" long hsa_match_gap_batch(hsa_index_t *ix, const hsa_regime_t *regimes, int n_regimes, const hsa_job_t *jobs,
@@ -481,12 +487,10 @@ extern "C" long hsa_match_gap_batch(hsa_index_t *ix, const hsa_regime_t *regimes
 {
     *hits_out = nullptr;
     if (n_jobs > 0 && (!mg || !widths || !widths_out)) { hsa_set_error("hsa_match_gap_batch: null argument"); return HSA_E_ARG; }
-    uint32_t *flags = (uint32_t *)malloc(sizeof(uint32_t) * ((size_t)n_jobs + 1));
+    std::vector<uint32_t> flags((size_t)(n_jobs > 0 ? n_jobs : 0) + 1);
     const MgHost mh{mg, widths, width_pairs, widths_out};
-    const long r = search_batch_impl(ix, regimes, n_regimes, jobs, n_jobs, codes, codes_len, n_aln, flags, hit_off,
-                                     hits_out, stats, &mh);
-    free(flags);
-    return r;
+    return search_batch_impl(ix, regimes, n_regimes, HostIn{jobs, n_jobs, codes, codes_len, &mh},
+                             HostOut{n_aln, flags.data(), hit_off, hits_out, stats});
 }
 
 extern "C" int hsa_search_device(hsa_index_t *ix, const hsa_regime_t *regimes, int n_regimes,
@@ -509,7 +513,6 @@ extern "C" int hsa_splice_seeds_device(hsa_index_t *ix, const hsa_regime_t *seed
     HSA_HIP(hipSetDevice(ix->device));
     hipStream_t st = stream ? (hipStream_t)stream : ix->stream;
     const uint32_t code_stride = (uint32_t)(2 * b->max_len), pair_stride = (uint32_t)(2 * b->max_len + 6);
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
     const size_t o_mg = al(calls * sizeof(hsa_job_t)), o_list = o_mg + al(calls * sizeof(hsa_mg_job_t));
     const size_t o_fl = o_list + al(calls * 4), o_cnt = o_fl + al(calls * 4), o_codes = o_cnt + 256;
     const size_t o_cw = o_codes + al(n * code_stride), total = o_cw + n * pair_stride * 8 + 256;
@@ -527,41 +530,18 @@ extern "C" int hsa_splice_seeds_device(hsa_index_t *ix, const hsa_regime_t *seed
     S.code_stride = code_stride; S.pair_stride = pair_stride;
     S.jobs = (hsa_job_t *)d; S.mg = (hsa_mg_job_t *)(d + o_mg); S.codes = (uint8_t *)(d + o_codes);
     S.cw = (int32_t *)(d + o_cw); S.list = (int32_t *)(d + o_list); S.count = cnt; S.ctr = ctr;
-    // the search pass zeroes the counters first; the width queries are added after it
-    void *before = ix->d_in;
-    if ((rc = hsa_grow(&ix->d_in, &ix->d_in_cap, 1536))) return rc;
-    int nb = 0;
-    if ((rc = stage_regimes(ix, seed_regime, 1, (char *)ix->d_in, nb, st, before != ix->d_in))) return rc;
-    const hsa_regime_t *d_reg = (const hsa_regime_t *)ix->d_in;
-    const uint8_t *d_bmap = (const uint8_t *)ix->d_in + 256;
-    const int seed_max = b->max_len / 3 + 2;
-    LaunchPlan P, B, H;
-    const bool wide = need_wide(seed_regime, 1);
-    if ((rc = plan_launch(ix, (int)calls, seed_max, 0, nb, false, wide, PASS_MAIN, P)) ||
-        (rc = plan_launch(ix, (int)calls, seed_max, 0, nb, false, wide, PASS_BIG, B)) ||
-        (rc = plan_launch(ix, (int)calls, seed_max, 0, nb, false, wide, PASS_HUGE, H, seed_regime->max_entries)))
-        return rc;
-    if ((rc = hsa_grow(&ix->d_ovf, &ix->d_ovf_cap, calls * 4 + 64)) ||
-        (rc = hsa_grow(&ix->d_ovf2, &ix->d_ovf2_cap, calls * 4 + 64)))
-        return rc;
-    HSA_HIP(hipMemsetAsync(ctr, 0, 16 * sizeof(unsigned long long), st));
+    RegimePlan C = regime_plan(seed_regime, 1);
+    C.nib_ok = false;
+    if ((rc = stage_regimes(ix, seed_regime, 1, C.nb, st))) return rc;
+    // the counters are zeroed here, before k_seed_prep adds the width queries to them
+    HSA_HIP(hipMemsetAsync(ctr, 0, CTR_SLOTS * sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_seed_prep, dim3((unsigned)((2 * n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, S);
     HSA_HIP(hipGetLastError());
     HSA_HIP(hipEventRecord(ix->ev0, st));
-    const MgPass mgp{S.mg, S.cw};
-    uint32_t *sfl = (uint32_t *)(d + o_fl);
-    // qctr 10: the pass's queue head, so that counter [7] (width queries) survives
-    if ((rc = launch_pass(ix, P, ix->main, d_reg, d_bmap, S.jobs, S.list, (int)calls, seed_max, 0, S.codes,
-                          b->d_n_aln, sfl, b->d_hit_off, b->d_hits, b->hit_cap, ctr, st, (int32_t *)ix->d_ovf, cnt, 10,
-                          &mgp)))
-        return rc;
-    if ((rc = launch_pass(ix, B, ix->big, d_reg, d_bmap, S.jobs, (const int32_t *)ix->d_ovf, (int)calls, seed_max, 0,
-                          S.codes, b->d_n_aln, sfl, b->d_hit_off, b->d_hits, b->hit_cap, ctr, st, (int32_t *)ix->d_ovf2,
-                          ctr + 8, 9, &mgp, 12)) ||
-        (rc = launch_pass(ix, H, ix->huge, d_reg, d_bmap, S.jobs, (const int32_t *)ix->d_ovf2, (int)calls, seed_max, 0,
-                          S.codes, b->d_n_aln, sfl, b->d_hit_off, b->d_hits, b->hit_cap, ctr, st, nullptr, ctr + 12, 15,
-                          &mgp)))
-        return rc;
+    const PassIO io{.jobs = S.jobs, .list = S.list, .n = (int)calls, .codes = S.codes, .n_aln = b->d_n_aln,
+                    .flags = (uint32_t *)(d + o_fl), .hit_off = b->d_hit_off, .hits = b->d_hits, .hit_cap = b->hit_cap,
+                    .ctr = ctr, .max_len = b->max_len / 3 + 2, .max_seed = 0, .mg = {S.mg, S.cw}};
+    if ((rc = run_capacity_passes(ix, C, io, PassLink{.n_dev = cnt, .qctr = CTR_Q_MG}, false, nullptr, st))) return rc;
     HSA_HIP(hipEventRecord(ix->ev1, st));
     return 0;
 }
@@ -777,31 +757,45 @@ __global__ void __launch_bounds__(BLOCK) k_pf_sa(PfSaArgs a, int fill)
     }
 }
 
-// The three capacity passes of caller-width searches over a device job list (as
-// hsa_splice_seeds_device runs them); counters ctr[16] zeroed here.
-static int mg_passes(hsa_index *ix, const hsa_regime_t *d_reg, const uint8_t *d_bmap, int nb, const hsa_job_t *jobs,
-                     const int32_t *list, const unsigned long long *n_dev, int n_upper, int max_len, bool gaps, bool wide,
-                     int max_entries, const uint8_t *codes, const MgPass &mgp, int32_t *d_n, uint32_t *d_fl,
-                     uint64_t *d_ho, uint32_t *d_hits, uint64_t hit_cap, unsigned long long *ctr, hipStream_t st)
+// the part of a prefetch's arguments that n reads of up to M bases and the index decide
+static PfArgs pf_args(const hsa_index *ix, uint32_t n, uint32_t M, int32_t seed_max_diff)
 {
-    int rc;
-    LaunchPlan P, B, H;
-    if ((rc = plan_launch(ix, n_upper, max_len, 0, nb, gaps, wide, PASS_MAIN, P)) ||
-        (rc = plan_launch(ix, n_upper, max_len, 0, nb, gaps, wide, PASS_BIG, B)) ||
-        (rc = plan_launch(ix, n_upper, max_len, 0, nb, gaps, wide, PASS_HUGE, H, max_entries)))
-        return rc;
-    if ((rc = hsa_grow(&ix->d_ovf, &ix->d_ovf_cap, (size_t)n_upper * 4 + 64)) ||
-        (rc = hsa_grow(&ix->d_ovf2, &ix->d_ovf2_cap, (size_t)n_upper * 4 + 64)))
-        return rc;
-    HSA_HIP(hipMemsetAsync(ctr, 0, 16 * sizeof(unsigned long long), st));
-    if ((rc = launch_pass(ix, P, ix->main, d_reg, d_bmap, jobs, list, n_upper, max_len, 0, codes, d_n, d_fl, d_ho, d_hits,
-                          hit_cap, ctr, st, (int32_t *)ix->d_ovf, n_dev, 10, &mgp)) ||
-        (rc = launch_pass(ix, B, ix->big, d_reg, d_bmap, jobs, (const int32_t *)ix->d_ovf, n_upper, max_len, 0, codes, d_n,
-                          d_fl, d_ho, d_hits, hit_cap, ctr, st, (int32_t *)ix->d_ovf2, ctr + 8, 9, &mgp, 12)) ||
-        (rc = launch_pass(ix, H, ix->huge, d_reg, d_bmap, jobs, (const int32_t *)ix->d_ovf2, n_upper, max_len, 0, codes,
-                          d_n, d_fl, d_ho, d_hits, hit_cap, ctr, st, nullptr, ctr + 12, 15, &mgp)))
-        return rc;
-    return 0;
+    PfArgs A;
+    A.fwd = RankDir{ix->blk[0], ix->isa0};
+    A.rev = RankDir{ix->blk[1], ix->risa0};
+    A.T = ix->T;
+    memcpy(A.C, ix->C, sizeof A.C);
+    A.n = n; A.max_len = M; A.sc = (M + 15u) / 16u * 16u + 16u; A.rs = M + 1u; A.cws = M / 3u + 3u > 13u ? M / 3u + 3u : 13u;
+    A.seed_max_diff = seed_max_diff;
+    A.ktd = trie_levels(ix, false);
+    A.ktw = A.ktd ? ix->d_trie_w : nullptr;
+    return A;
+}
+
+// What the seed and the anchor passes of a prefetch share: both regimes' staging, the
+// calls k_pf_seeds and k_pf_anchors built, the calls' hit offsets.
+struct PfSearch {
+    int nb;
+    bool wide;
+    const hsa_regime_t *seed_rg, *anchor_rg;
+    const PfArgs *A;
+    uint64_t *call_hit;
+};
+
+// The capacity passes of the seed calls (regime 0), or of the anchor calls (regime 1, 12
+// bases): caller-width searches over the calls listed on the device (n_dev of them, at most
+// n_upper), hits and counters (zeroed here) in their own regions.
+static int pf_passes(hsa_index *ix, const PfSearch &F, bool anchors, const unsigned long long *n_dev, int n_upper,
+                     uint32_t *hits, uint64_t hit_cap, unsigned long long *ctr, hipStream_t st)
+{
+    const PfArgs &A = *F.A;
+    RegimePlan C = regime_plan(anchors ? F.anchor_rg : F.seed_rg, 1);
+    C.nb = F.nb; C.wide = F.wide; C.nib_ok = false;
+    // the caller widths are at rows + wb_off (a row's prefix, or cw + call * cws)
+    const PassIO io{.jobs = A.jobs, .list = A.list + (anchors ? 6 * (size_t)A.n : 0), .n = n_upper, .codes = A.scodes,
+                    .n_aln = A.call_n, .flags = A.call_fl, .hit_off = F.call_hit, .hits = hits, .hit_cap = hit_cap,
+                    .ctr = ctr, .max_len = anchors ? 12 : (int)(A.max_len / 3u + 2u), .max_seed = 0, .mg = {A.mg, A.rows}};
+    return run_capacity_passes(ix, C, io, PassLink{.n_dev = n_dev, .qctr = CTR_Q_MG}, true, nullptr, st);
 }
 
 // The prefetch pass, and with ext_rg the splice kernel after it (hsa_splice.hip): res
@@ -838,9 +832,9 @@ static int pf_batch(hsa_index_t *ix, const hsa_regime_t *seed_rg, const hsa_regi
     hipStream_t st = ix->stream;
     const double t0 = [] { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec + 1e-9 * t.tv_nsec; }();
     const size_t N = (size_t)n, calls = 8 * N;
-    const uint32_t sc = (M + 15u) / 16u * 16u + 16u, rs = M + 1u, cws = M / 3u + 3u > 13u ? M / 3u + 3u : 13u;
+    PfArgs A = pf_args(ix, (uint32_t)N, M, seed_rg->max_diff);
+    const uint32_t sc = A.sc, rs = A.rs, cws = A.cws;
     const uint64_t cap_s = 6 * N * 16 + 65536, cap_a = 2 * N * 16 + 16384;
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
     // device layout
     size_t o = 0;
     const size_t o_lens = o; o += al(N * 4);
@@ -869,15 +863,8 @@ static int pf_batch(hsa_index_t *ix, const hsa_regime_t *seed_rg, const hsa_regi
                        *satot = ctr_s + 33, *scnt = ctr_s + 34;
     HSA_HIP(hipMemsetAsync(ctr_s, 0, 1024, st));
     char *dq = d + o_out;
-    PfArgs A;
-    A.fwd = RankDir{ix->blk[0], ix->isa0};
-    A.rev = RankDir{ix->blk[1], ix->risa0};
-    A.T = ix->T;
-    memcpy(A.C, ix->C, sizeof A.C);
-    A.n = (uint32_t)n; A.max_len = M; A.sc = sc; A.rs = rs; A.cws = cws;
     A.lens = (const uint32_t *)(d + o_lens); A.offs = (const uint64_t *)(d + o_offs);
     A.codes = (const uint8_t *)(d + o_codes); A.amd = (const int32_t *)(d + o_amd);
-    A.seed_max_diff = seed_rg->max_diff;
     A.scodes = (uint8_t *)(d + o_sc);
     A.rows = (int32_t *)(dq + q_rows);
     A.jobs = (hsa_job_t *)(d + o_jobs); A.mg = (hsa_mg_job_t *)(d + o_mg);
@@ -886,33 +873,19 @@ static int pf_batch(hsa_index_t *ix, const hsa_regime_t *seed_rg, const hsa_regi
     A.acount = acnt;
     A.d_n = nullptr;
     A.cwd = (q_cw - q_rows) / 8;
-    {
-        const char *te = getenv("HSA_TRIE");
-        const bool tr = ix->trie_depth > 0 && !ix->trie_wide && !(te && atoi(te) == 0);
-        A.ktw = tr ? ix->d_trie_w : nullptr;
-        A.ktd = tr ? ix->trie_depth : 0u;
-    }
     A.prefix = ext_rg ? 1u : 0u;             // the host tables want every call's width_back after it
     HSA_HIP(hipMemsetAsync(d + o_sc, 4, 2 * N * sc + 64, st));         // padding reads as N
     hipLaunchKernelGGL(k_pf_rows, dim3((unsigned)((6 * N + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, A);
     hipLaunchKernelGGL(k_pf_seeds, dim3((unsigned)((6 * N + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, A);
     HSA_HIP(hipGetLastError());
     // both regimes staged once: seeds use regime 0, anchors regime 1
-    void *before = ix->d_in;
-    if ((rc = hsa_grow(&ix->d_in, &ix->d_in_cap, 1536))) return rc;
-    int nb = 0;
-    if ((rc = stage_regimes(ix, rg2, 2, (char *)ix->d_in, nb, st, before != ix->d_in))) return rc;
-    const hsa_regime_t *d_reg = (const hsa_regime_t *)ix->d_in;
-    const uint8_t *d_bmap = (const uint8_t *)ix->d_in + 256;
-    const bool wide = need_wide(rg2, 2);
-    const MgPass mgp{A.mg, A.rows};          // widths at rows + wb_off (a row's prefix, or cw + call * cws)
+    PfSearch F{.nb = 0, .wide = regime_plan(rg2, 2).wide, .seed_rg = seed_rg, .anchor_rg = anchor_rg, .A = &A,
+               .call_hit = (uint64_t *)(dq + q_ho)};
+    if ((rc = stage_regimes(ix, rg2, 2, F.nb, st))) return rc;
     const unsigned long long n_seed = 6 * N;
     HSA_HIP(hipMemcpyAsync(scnt, &n_seed, 8, hipMemcpyHostToDevice, st));
     HSA_HIP(hipEventRecord(ix->ev0, st));
-    if ((rc = mg_passes(ix, d_reg, d_bmap, nb, A.jobs, A.list, scnt, (int)(6 * N), (int)(M / 3u + 2u), false, wide,
-                        seed_rg->max_entries, A.scodes, mgp, A.call_n, A.call_fl, (uint64_t *)(dq + q_ho),
-                        (uint32_t *)(dq + q_hs), cap_s, ctr_s, st)))
-        return rc;
+    if ((rc = pf_passes(ix, F, false, scnt, (int)(6 * N), (uint32_t *)(dq + q_hs), cap_s, ctr_s, st))) return rc;
     hipLaunchKernelGGL(k_pf_anchors, dim3((unsigned)((2 * N + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, A);
     HSA_HIP(hipGetLastError());
     // the anchors' pass is planned for the anchors there are (a gapped regime's pool per
@@ -920,10 +893,7 @@ static int pf_batch(hsa_index_t *ix, const hsa_regime_t *seed_rg, const hsa_regi
     unsigned long long n_anchor = 0;
     HSA_HIP(hipMemcpyAsync(&n_anchor, acnt, 8, hipMemcpyDeviceToHost, st));
     HSA_HIP(hipStreamSynchronize(st));
-    if (n_anchor &&
-        (rc = mg_passes(ix, d_reg, d_bmap, nb, A.jobs, A.list + 6 * N, acnt, (int)n_anchor, 12,
-                        anchor_rg->max_gapo > 0, wide, anchor_rg->max_entries, A.scodes, mgp, A.call_n, A.call_fl,
-                        (uint64_t *)(dq + q_ho), (uint32_t *)(dq + q_ha), cap_a, ctr_a, st)))
+    if (n_anchor && (rc = pf_passes(ix, F, true, acnt, (int)n_anchor, (uint32_t *)(dq + q_ha), cap_a, ctr_a, st)))
         return rc;
     // unfinished calls (hits past the caps, stacks past the HUGE pass) are not answered
     PfSaArgs S;
@@ -976,7 +946,8 @@ static int pf_batch(hsa_index_t *ix, const hsa_regime_t *seed_rg, const hsa_regi
     }
     HSA_HIP(hipEventRecord(ix->ev1, st));
     // one copy of the output block (hits up to their counts) into pinned host memory
-    const uint64_t nh_s = hc[1] < cap_s ? hc[1] : cap_s, nh_a = hc[16 + 1] < cap_a ? hc[16 + 1] : cap_a;
+    const uint64_t nh_s = hc[CTR_HITS] < cap_s ? hc[CTR_HITS] : cap_s;
+    const uint64_t nh_a = hc[CTR_SLOTS + CTR_HITS] < cap_a ? hc[CTR_SLOTS + CTR_HITS] : cap_a;
     const size_t h_need = q_hs + (nh_s + nh_a) * 36 + al(n_sa * 16) + 256;
     if (h_need > ix->h_pf_cap) {
         if (ix->h_pf) (void)hipHostFree(ix->h_pf);
@@ -1052,8 +1023,8 @@ __global__ void k_sp_stats(const unsigned long long *cnt, const unsigned long lo
                            const unsigned long long *ctr_a, unsigned long long *out)
 {
     out[0] = *cnt;
-    out[5] = ctr_s[2] + ctr_s[7] + ctr_a[2] + ctr_a[7];
-    out[6] = ctr_s[1] + ctr_a[1];
+    out[5] = ctr_s[CTR_RANK] + ctr_s[CTR_WIDTH_Q] + ctr_a[CTR_RANK] + ctr_a[CTR_WIDTH_Q];
+    out[6] = ctr_s[CTR_HITS] + ctr_a[CTR_HITS];
 }
 
 extern "C" int hsa_splice_device(hsa_index_t *ix, const hsa_regime_t *seed_rg, const hsa_regime_t *anchor_rg,
@@ -1075,9 +1046,9 @@ extern "C" int hsa_splice_device(hsa_index_t *ix, const hsa_regime_t *seed_rg, c
     hipStream_t st = stream ? (hipStream_t)stream : ix->stream;
     const size_t N = (size_t)b->n_jobs, calls = 8 * N;
     const uint32_t M = (uint32_t)b->max_len;
-    const uint32_t sc = (M + 15u) / 16u * 16u + 16u, rs = M + 1u, cws = M / 3u + 3u > 13u ? M / 3u + 3u : 13u;
+    PfArgs A = pf_args(ix, (uint32_t)N, M, seed_rg->max_diff);
+    const uint32_t sc = A.sc, rs = A.rs, cws = A.cws;
     const uint64_t cap_s = 6 * N * 16 + 65536, cap_a = 2 * N * 16 + 16384;
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
     size_t o = 0;
     const size_t o_lens = o; o += al(N * 4);
     const size_t o_offs = o; o += al(N * 8);
@@ -1102,15 +1073,8 @@ extern "C" int hsa_splice_device(hsa_index_t *ix, const hsa_regime_t *seed_rg, c
     unsigned long long *out_ctr = (unsigned long long *)b->d_counters;
     HSA_HIP(hipMemsetAsync(ctr_s, 0, 1024, st));
     HSA_HIP(hipMemsetAsync(out_ctr, 0, 8 * sizeof(unsigned long long), st));
-    PfArgs A;
-    A.fwd = RankDir{ix->blk[0], ix->isa0};
-    A.rev = RankDir{ix->blk[1], ix->risa0};
-    A.T = ix->T;
-    memcpy(A.C, ix->C, sizeof A.C);
-    A.n = (uint32_t)N; A.max_len = M; A.sc = sc; A.rs = rs; A.cws = cws;
     A.lens = (const uint32_t *)(d + o_lens); A.offs = (const uint64_t *)(d + o_offs);
     A.codes = b->d_codes; A.amd = (const int32_t *)(d + o_amd);
-    A.seed_max_diff = seed_rg->max_diff;
     A.scodes = (uint8_t *)(d + o_sc);
     A.rows = (int32_t *)(d + o_rows);
     A.jobs = (hsa_job_t *)(d + o_jobs); A.mg = (hsa_mg_job_t *)(d + o_mg);
@@ -1119,12 +1083,6 @@ extern "C" int hsa_splice_device(hsa_index_t *ix, const hsa_regime_t *seed_rg, c
     A.acount = acnt;
     A.d_n = rcnt;
     A.cwd = (o_cw - o_rows) / 8;
-    {
-        const char *te = getenv("HSA_TRIE");
-        const bool tr = ix->trie_depth > 0 && !ix->trie_wide && !(te && atoi(te) == 0);
-        A.ktw = tr ? ix->d_trie_w : nullptr;
-        A.ktd = tr ? ix->trie_depth : 0u;
-    }
     A.prefix = 1;
     const unsigned grid_n = (unsigned)((N + BLOCK - 1) / BLOCK);
     hipLaunchKernelGGL(k_sp_prep, dim3(grid_n), dim3(BLOCK), 0, st, b->d_jobs, b->d_flags, b->d_n_aln, (uint32_t)N,
@@ -1135,26 +1093,15 @@ extern "C" int hsa_splice_device(hsa_index_t *ix, const hsa_regime_t *seed_rg, c
     hipLaunchKernelGGL(k_pf_rows, dim3((unsigned)((6 * N + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, A);
     hipLaunchKernelGGL(k_pf_seeds, dim3((unsigned)((6 * N + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, A);
     HSA_HIP(hipGetLastError());
-    void *before = ix->d_in;
-    if ((rc = hsa_grow(&ix->d_in, &ix->d_in_cap, 1536))) return rc;
-    int nb = 0;
-    if ((rc = stage_regimes(ix, rg2, 2, (char *)ix->d_in, nb, st, before != ix->d_in))) return rc;
-    const hsa_regime_t *d_reg = (const hsa_regime_t *)ix->d_in;
-    const uint8_t *d_bmap = (const uint8_t *)ix->d_in + 256;
-    const bool wide = need_wide(rg2, 2);
-    const MgPass mgp{A.mg, A.rows};          // widths at rows + wb_off (a row's prefix, or cw + call * cws)
+    PfSearch F{.nb = 0, .wide = regime_plan(rg2, 2).wide, .seed_rg = seed_rg, .anchor_rg = anchor_rg, .A = &A,
+               .call_hit = (uint64_t *)(d + o_ho)};
+    if ((rc = stage_regimes(ix, rg2, 2, F.nb, st))) return rc;
     // no host round trip: the passes take their job counts from the device (the seed
     // calls' 6 per read, the anchors k_pf_anchors listed), planned for their upper bounds
-    if ((rc = mg_passes(ix, d_reg, d_bmap, nb, A.jobs, A.list, scnt, (int)(6 * N), (int)(M / 3u + 2u), false, wide,
-                        seed_rg->max_entries, A.scodes, mgp, A.call_n, A.call_fl, (uint64_t *)(d + o_ho),
-                        (uint32_t *)(d + o_hs), cap_s, ctr_s, st)))
-        return rc;
+    if ((rc = pf_passes(ix, F, false, scnt, (int)(6 * N), (uint32_t *)(d + o_hs), cap_s, ctr_s, st))) return rc;
     hipLaunchKernelGGL(k_pf_anchors, dim3((unsigned)((2 * N + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, A);
     HSA_HIP(hipGetLastError());
-    if ((rc = mg_passes(ix, d_reg, d_bmap, nb, A.jobs, A.list + 6 * N, acnt, (int)(2 * N), 12, anchor_rg->max_gapo > 0,
-                        wide, anchor_rg->max_entries, A.scodes, mgp, A.call_n, A.call_fl, (uint64_t *)(d + o_ho),
-                        (uint32_t *)(d + o_ha), cap_a, ctr_a, st)))
-        return rc;
+    if ((rc = pf_passes(ix, F, true, acnt, (int)(2 * N), (uint32_t *)(d + o_ha), cap_a, ctr_a, st))) return rc;
     PfDev pd;
     pd.n = (uint32_t)N; pd.max_len = M; pd.sc = sc; pd.rs = rs; pd.cws = cws;
     pd.lens = A.lens; pd.amd = A.amd; pd.scodes = A.scodes; pd.rows = A.rows; pd.cw = A.cw;

@@ -4,7 +4,7 @@
 // instantiated with IT = uint64_t: the same 16-byte rank blocks, counts modulo 2^32,
 // with the index's count-wrap table for the high words (RankDir64, hsa_device.h),
 // 32-byte stack entries, hsa_aln64_t hit records.
-#include "hsa_search_kernels.h"
+#include "hsa_search_launch.h"
 
 extern "C" int hsa_search_device64(hsa_index_t *ix, const hsa_regime_t *regimes, int n_regimes,
                                    const hsa_device_batch_t *b, void *stream)

@@ -381,7 +381,7 @@ __global__ void __launch_bounds__(64) k_search_any(AnyArgs a)
                     if (sk[si] <= sl[si]) push(i, sk[si], sl[si], srk[si], srl[si], e.mm, e.go, e.ge, ST_M, 0);
                 }
             }
-            if (err) { atomicAdd(&a.ctr[5], 1ull); fl = HSA_F_OVERFLOW; done = true; break; }
+            if (err) { atomicAdd(&a.ctr[CTR_ERRORS], 1ull); fl = HSA_F_OVERFLOW; done = true; break; }
             if (ovf) { fl = HSA_F_OVERFLOW; done = true; break; }
             if (M && !(seed_kind == HSA_SEED_ALIAS && M->ws_off == HSA_MG_PREFIX)) {   // width_back back (Q6)
                 int32_t *w = a.cw + 2 * M->wb_off;
@@ -389,7 +389,7 @@ __global__ void __launch_bounds__(64) k_search_any(AnyArgs a)
             }
             if (n_aln > 0 || M) {
                 if (n_aln > 0) {
-                    const unsigned long long o = atomicAdd(&a.ctr[1], (unsigned long long)n_aln);
+                    const unsigned long long o = atomicAdd(&a.ctr[CTR_HITS], (unsigned long long)n_aln);
                     if (o + (uint64_t)n_aln > a.hit_cap) { fl = HSA_F_OVERFLOW; done = true; break; }
                     uint32_t *dst = a.hits + o * OW;
                     for (int h = 0; h < n_aln; ++h) {
@@ -417,7 +417,7 @@ __global__ void __launch_bounds__(64) k_search_any(AnyArgs a)
         if (fl & HSA_F_OVERFLOW) {
             n_out = 0; out_off = 0;
             if (a.ovf_list) a.ovf_list[atomicAdd(a.ovf_n, 1ull)] = job;
-            else atomicAdd(&a.ctr[11], 1ull);
+            else atomicAdd(&a.ctr[CTR_UNFINISHED], 1ull);
         }
         a.n_aln[job] = n_out;
         a.flags[job] = fl;
@@ -426,10 +426,10 @@ __global__ void __launch_bounds__(64) k_search_any(AnyArgs a)
         st_q = st_wq = st_fq = st_b = st_p = 0;
     }
     st_q = tq; st_wq = twq; st_fq = tfq; st_b = tb; st_p = tp;
-    atomicAdd(&a.ctr[2], (unsigned long long)st_q);
-    atomicAdd(&a.ctr[3], (unsigned long long)st_b);
-    atomicAdd(&a.ctr[4], (unsigned long long)st_p);
-    atomicAdd(&a.ctr[7], (unsigned long long)st_wq);
-    atomicAdd(&a.ctr[13], (unsigned long long)st_fq);
-    atomicAdd(&a.ctr[14], (unsigned long long)st_fq);
+    atomicAdd(&a.ctr[CTR_RANK], (unsigned long long)st_q);
+    atomicAdd(&a.ctr[CTR_SECTORS], (unsigned long long)st_b);
+    atomicAdd(&a.ctr[CTR_POPS], (unsigned long long)st_p);
+    atomicAdd(&a.ctr[CTR_WIDTH_Q], (unsigned long long)st_wq);
+    atomicAdd(&a.ctr[CTR_FWD_Q_ALL], (unsigned long long)st_fq);
+    atomicAdd(&a.ctr[CTR_FWD_Q_REF], (unsigned long long)st_fq);
 }

@@ -1,8 +1,9 @@
 #pragma once
 // hsa_search_kernels.h -- the bwa_cal_sa_reg_gap per-read loop as two persistent kernels
 // (templated on the interval type: 32-bit, the reference's bwtint_t, and 64-bit for
-// texts of 2^32 characters or more), and the host helpers that plan and launch them.
-// Included by hsa_search.hip (32-bit API) and hsa_search64.hip (64-bit API).
+// texts of 2^32 characters or more).  The host side that plans and launches them is
+// hsa_search_launch.h, which hsa_search.hip (32-bit API) and hsa_search64.hip (64-bit
+// API) include.
 //
 // k_widths: bwt_cal_width (bwtaln.c:73-98) for every (read, strand) of the batch --
 //   the seed width and the whole-read width of the rc and the fwd strand, one work
@@ -78,8 +79,7 @@ struct SearchArgs {
     uint64_t *hit_off;
     uint32_t *hits;
     uint64_t hit_cap;
-    unsigned long long *ctr;       // [0] queue head [1] hit alloc [2] rank queries [3] blocks [4] pops [5] errors
-                                   // [6] width item queue head
+    unsigned long long *ctr;       // the search's 16 counters (the CTR_* slots, hsa_internal.h)
     const uint8_t *wb, *ws;        // width rows of k_widths (row = list position * 2 + strand),
     uint32_t *wg;                  //   64 rows interleaved; wg: full w values (gap_shadow only)
     uint32_t rb, rs, rg;           //   row capacities: bytes, bytes, words
@@ -91,7 +91,7 @@ struct SearchArgs {
     uint32_t nib_wb, nib_ws;              // 4-bit layout: LDS words per lane of the read / seed row
     uint32_t mm_buckets;           // 1: the bucket of every score is its n_mm (no gap opens, s_mm > 0)
     // device-side overflow re-run: the main pass appends reads that exceeded their
-    // lane's capacity to ovf_list (count in ctr[8]); the re-run pass takes its read
+    // lane's capacity to ovf_list (count in ctr[ovf_ctr]); the re-run pass takes its read
     // count from n_dev and its queue head from ctr[qctr]
     int32_t *ovf_list;
     const unsigned long long *n_dev;
@@ -542,7 +542,7 @@ __device__ __forceinline__ void wave_add(unsigned long long *c, unsigned long lo
 
 // One lane per row (rows in order): row = list position * 2 + strand.  The forward
 // strand's rows are computed speculatively and count as the reference's work only
-// when k_search searches that strand (ctr[13]: all of them).
+// when k_search searches that strand (ctr[CTR_FWD_Q_ALL]: all of them).
 template <typename WT, typename IT = uint32_t>
 __global__ void __launch_bounds__(BLOCK) k_widths(SearchArgs a)
 {
@@ -557,11 +557,11 @@ __global__ void __launch_bounds__(BLOCK) k_widths(SearchArgs a)
         if (a.wkey) a.wkey[R] = cost_key(a, w);
     }
     // rank queries: the reverse-complement strand is always searched (bwtaln.c:343)
-    wave_add(&a.ctr[2], strand ? w.q : 0u);
-    wave_add(&a.ctr[7], strand ? w.q : 0u);
-    wave_add(&a.ctr[13], strand ? 0u : w.q);
-    wave_add(&a.ctr[3], w.b);
-    wave_add(&a.ctr[10], w.t);
+    wave_add(&a.ctr[CTR_RANK], strand ? w.q : 0u);
+    wave_add(&a.ctr[CTR_WIDTH_Q], strand ? w.q : 0u);
+    wave_add(&a.ctr[CTR_FWD_Q_ALL], strand ? 0u : w.q);
+    wave_add(&a.ctr[CTR_SECTORS], w.b);
+    wave_add(&a.ctr[CTR_TRIE], w.t);
 }
 
 // One lane per read, one strand's row each.
@@ -607,12 +607,12 @@ __global__ void __launch_bounds__(BLOCK) k_widths_reads(SearchArgs a, uint32_t m
         if (more) list2[b + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)p;
     }
     const uint32_t rq = mode == 1 ? w.q : 0u, fq = mode == 2 ? w.q : 0u, sq = mode == 3 ? w.q : 0u;
-    wave_add(&a.ctr[2], rq + fq);
-    wave_add(&a.ctr[7], rq + fq);
-    wave_add(&a.ctr[13], fq + sq);
-    wave_add(&a.ctr[14], fq);
-    wave_add(&a.ctr[3], w.b);
-    wave_add(&a.ctr[10], w.t);
+    wave_add(&a.ctr[CTR_RANK], rq + fq);
+    wave_add(&a.ctr[CTR_WIDTH_Q], rq + fq);
+    wave_add(&a.ctr[CTR_FWD_Q_ALL], fq + sq);
+    wave_add(&a.ctr[CTR_FWD_Q_REF], fq);
+    wave_add(&a.ctr[CTR_SECTORS], w.b);
+    wave_add(&a.ctr[CTR_TRIE], w.t);
 }
 
 // Caller-width mode: the width rows of each call from the caller's bwt_width_t pairs
@@ -746,7 +746,7 @@ static __global__ void __launch_bounds__(BLOCK) k_split_finalize(SearchArgs a)
         if (nr < 0 || (nr == 0 && nf < 0)) {
             fl = HSA_F_OVERFLOW;
             if (a.ovf_list) a.ovf_list[atomicAdd(&a.ctr[a.ovf_ctr], 1ull)] = job;
-            else atomicAdd(&a.ctr[11], 1ull);
+            else atomicAdd(&a.ctr[CTR_UNFINISHED], 1ull);
         } else if (nr > 0) {
             na = nr; off = a.sp_off[2 * q];
             q_add = a.sp_q[2 * q]; p_add = a.sp_p[2 * q];
@@ -768,9 +768,9 @@ static __global__ void __launch_bounds__(BLOCK) k_split_finalize(SearchArgs a)
         w_add += __shfl_xor(w_add, d);
     }
     if ((threadIdx.x & 63) == 0) {
-        if (q_add) atomicAdd(&a.ctr[2], q_add);
-        if (p_add) atomicAdd(&a.ctr[4], p_add);
-        if (w_add) { atomicAdd(&a.ctr[7], w_add); atomicAdd(&a.ctr[14], w_add); }
+        if (q_add) atomicAdd(&a.ctr[CTR_RANK], q_add);
+        if (p_add) atomicAdd(&a.ctr[CTR_POPS], p_add);
+        if (w_add) { atomicAdd(&a.ctr[CTR_WIDTH_Q], w_add); atomicAdd(&a.ctr[CTR_FWD_Q_REF], w_add); }
     }
 }
 
@@ -1051,7 +1051,7 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
         }
         if (fl & HSA_F_OVERFLOW) {
             if (r->ovf_list) r->ovf_list[atomicAdd(&r->ctr[r->ovf_ctr], 1ull)] = job;   // re-run by the next pass
-            else atomicAdd(&r->ctr[11], 1ull);                                  // the last pass: stays unfinished
+            else atomicAdd(&r->ctr[CTR_UNFINISHED], 1ull);                       // the last pass: stays unfinished
         }
         r->n_aln[job] = na;
         r->flags[job] = fl;
@@ -1078,7 +1078,7 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
         }
         if (n_aln > 0) {
             const ColdArgs r = cold_args();
-            const unsigned long long o = atomicAdd(&r->ctr[1], (unsigned long long)n_aln);
+            const unsigned long long o = atomicAdd(&r->ctr[CTR_HITS], (unsigned long long)n_aln);
             if (o + (uint64_t)n_aln > r->hit_cap) { finish_job(HSA_F_OVERFLOW, 0, 0); return; }
             uint32_t *dst = r->hits + o * OW;
             const uint32_t s30 = C_STRAND(ctl) << 30;
@@ -1466,7 +1466,7 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
                         break;
                     }
                 }
-                if (C_OVF(ctl) > 1) atomicAdd(&cold_args()->ctr[5], 1ull);
+                if (C_OVF(ctl) > 1) atomicAdd(&cold_args()->ctr[CTR_ERRORS], 1ull);
                 finish_job(HSA_F_OVERFLOW, 0, 0);
                 break;
             }
@@ -1805,13 +1805,13 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
             if (lane == 0) { atomicAdd(&a.fr_c[6], hs); atomicAdd(&a.fr_c[8], hq); }
         }
     }
-    atomicAdd(&a.ctr[2], (unsigned long long)st_q);
-    atomicAdd(&a.ctr[3], (unsigned long long)st_b);
-    atomicAdd(&a.ctr[4], (unsigned long long)st_p);
+    atomicAdd(&a.ctr[CTR_RANK], (unsigned long long)st_q);
+    atomicAdd(&a.ctr[CTR_SECTORS], (unsigned long long)st_b);
+    atomicAdd(&a.ctr[CTR_POPS], (unsigned long long)st_p);
     if (st_wq) {
-        atomicAdd(&a.ctr[2], (unsigned long long)st_wq);
-        atomicAdd(&a.ctr[7], (unsigned long long)st_wq);
-        atomicAdd(&a.ctr[14], (unsigned long long)st_wq);
+        atomicAdd(&a.ctr[CTR_RANK], (unsigned long long)st_wq);
+        atomicAdd(&a.ctr[CTR_WIDTH_Q], (unsigned long long)st_wq);
+        atomicAdd(&a.ctr[CTR_FWD_Q_REF], (unsigned long long)st_wq);
     }
 #undef HEAD
 #undef WB
@@ -1828,690 +1828,7 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
 #undef SCORE
 }
 
-
-
 #include "hsa_search_any.h"
-
-// ---------------------------------------------------------------- host helpers (both TUs)
-// What any search accepts (k_search_any's bounds); fast_regimes: what k_search's layouts hold.
-static int check_regimes(const hsa_regime_t *rg, int n)
-{
-    for (int r = 0; r < n; ++r) {
-        const hsa_regime_t &R = rg[r];
-        if (R.s_mm < 0 || R.s_gapo < 0 || R.s_gape < 0) { hsa_set_error("negative penalty"); return HSA_E_ARG; }
-        if (R.n_stacks <= 0 || R.n_stacks > ANY_MAX_STACKS) {
-            hsa_set_error("n_stacks %d outside 1..%d", R.n_stacks, ANY_MAX_STACKS);
-            return HSA_E_ARG;
-        }
-        if (R.max_gapo < 0 || R.max_gape < 0) { hsa_set_error("max_gapo/max_gape negative"); return HSA_E_ARG; }
-        if (R.max_diff < -1) { hsa_set_error("max_diff out of range"); return HSA_E_ARG; }
-    }
-    return 0;
-}
-
-// Dense bucket numbering of the scores a search of this regime can push
-// (bwtgap.c:46-75): n_mm <= max_diff+1, n_gapo <= min(max_gapo, max_diff), n_gape > 0
-// only after a gap open.  Returns the bucket count.
-static int bucket_map(const hsa_regime_t &R, uint8_t map[MAXS])
-{
-    bool used[MAXS] = {false};
-    const int md = R.max_diff < 0 ? 0 : R.max_diff;
-    const int go_max = R.max_gapo < md ? R.max_gapo : md;
-    for (int mm = 0; mm <= md + 1; ++mm)
-        for (int go = 0; go <= go_max; ++go)
-            for (int ge = 0; ge <= (go > 0 ? R.max_gape : 0); ++ge) {
-                const int s = mm * R.s_mm + go * R.s_gapo + ge * R.s_gape;
-                if (s >= 0 && s < MAXS && s < R.n_stacks) used[s] = true;
-            }
-    int k = 0;
-    for (int s = 0; s < MAXS; ++s) map[s] = used[s] && k < 0xFF ? (uint8_t)k++ : (uint8_t)0xFF;
-    return k;
-}
-
-// Regimes whose every bound fits k_search's layouts: the entry meta word (n_gapo 4
-// bits, n_gape 8, n_mm 7), the score table (MAXS), the bucket mask (MAXB reachable
-// scores) and the 16-bit pruning elements (bids compared with bounds <= 254).  Other
-// regimes run k_search_any.
-static bool fast_regimes(const hsa_regime_t *rg, int n)
-{
-    if (getenv("HSA_FORCE_ANY")) return false;       // tests: every search through k_search_any
-    for (int r = 0; r < n; ++r) {
-        const hsa_regime_t &R = rg[r];
-        if (R.max_gapo > 14 || R.max_gape > 254 || R.max_diff > 125 || R.max_seed_diff > 254 || R.n_stacks > MAXS)
-            return false;
-        uint8_t map[MAXS];
-        if (bucket_map(R, map) > MAXB) return false;
-    }
-    return true;
-}
-
-#define FAST_MAX_LEN 1023u       // k_search: 10-bit read positions (meta word, control word)
-
-// The dense bucket of a score is simply its n_mm when no gap opens exist and every
-// reachable mismatch count has its own score (k_search skips the table then).
-static bool mm_buckets(const hsa_regime_t *rg, int n, const uint8_t *bmap)
-{
-    for (int r = 0; r < n; ++r) {
-        const hsa_regime_t &R = rg[r];
-        if (R.max_gapo != 0 || R.s_mm <= 0) return false;
-        const int md = R.max_diff < 0 ? 0 : R.max_diff;
-        for (int mm = 0; mm <= md + 1; ++mm) {
-            const int sc = mm * R.s_mm;
-            if (sc >= MAXS || bmap[r * MAXS + sc] != mm) return false;
-        }
-    }
-    return true;
-}
-
-struct LaunchPlan {
-    size_t lanes, blocks;
-    uint32_t nt;                     // lanes per workgroup of k_search (256 or 64)
-    uint32_t pcap, hcap, nb;
-    bool gaps, wide;                 // gap opens possible; 16-bit pruning elements (WFmt)
-    bool nib;                        // 4-bit pruning elements in LDS (WFmt<WNib>)
-    uint32_t off_heads, off_wb, off_ws;
-    uint32_t nib_wb, nib_ws;         // 4-bit rows: LDS words per lane (SearchArgs)
-    size_t lds;
-    bool huge;                       // PASS_HUGE: 32-bit links, reused slots
-    uint32_t ntab;                   // score table entries per regime in LDS
-    size_t resident;                 // lanes resident on the chip (every CU full)
-    size_t res_lanes = 0;            // lanes the scratch is reserved for (BIG: all its lanes)
-};
-
-// The capacity passes of one search: MAIN (every read), BIG (the reads that overflowed
-// their main-pass lane: 65 535 pool slots, 16 384 hits), HUGE (the reads that overflowed
-// BIG: reused slots up to max_entries + 16 live entries, 262 144 hits).
-enum { PASS_MAIN = 0, PASS_BIG = 1, PASS_HUGE = 2 };
-
-static int plan_launch(hsa_index *ix, int n_jobs, int max_len, int max_seed, int nb, bool gaps, bool wide, int mode,
-                       LaunchPlan &P, int max_entries = 0, uint32_t ent_bytes = 16, bool nib_ok = false)
-{
-    const bool big = mode == PASS_BIG;
-    P.huge = mode == PASS_HUGE;
-    P.ntab = (uint32_t)ix->staged_ntab;
-    P.nb = (uint32_t)nb;
-    P.gaps = gaps;
-    P.wide = wide;
-    const uint32_t esz = wide ? 2u : 1u;
-    P.nib = false;
-    // Resident workgroups per CU, from gfx950's own limits: 160 KiB of LDS per CU, at
-    // most 16 waves (__launch_bounds__(NT, 4) caps VGPRs at 4 waves per SIMD).  The
-    // per-lane LDS (bucket heads, pruning rows) decides between 256-lane workgroups
-    // and 64-lane ones, which pack the CU's LDS more finely: -n 4 -o 1 has 39 buckets
-    // and ~220 B per lane, i.e. 2 workgroups of 256 (8 waves) but 11 of 64 (11 waves).
-    // (hipOccupancyMaxActiveBlocksPerMultiprocessor is not used: depending on which
-    // HIP runtime the process loaded first it assumed 64 KiB of LDS and halved the
-    // grid -- measured 512 instead of 1024 workgroups, 1.5x slower.)
-    auto layout = [&](uint32_t nt) {
-        const uint32_t epw = P.nib ? 8u : 4u / esz;      // elements per LDS word (WFmt::EPW)
-        P.nt = nt;
-        P.off_heads = 2 * P.ntab + 128;   // score tables, then the two regimes
-        P.off_wb = P.off_heads + (uint32_t)nb * nt * (P.huge ? 4u : 2u);
-        // k_search reads elements 0 .. len - 1 of a row (pops of position i read i - 1,
-        // expansions i - 1 and i < len; seed rows ii - 1 and ii < seed_len): the 4-bit
-        // rows keep just those, which takes config 5's 64-lane workgroups from 15 to 16
-        // per CU; the 8-bit rows keep element len too (the LDS-DMA copies whole words)
-        P.nib_wb = ((uint32_t)max_len + 7u) / 8u;
-        P.nib_ws = ((uint32_t)max_seed + 7u) / 8u;
-        const uint32_t wbw = P.nib ? P.nib_wb : (uint32_t)max_len / epw + 1u;
-        const uint32_t wsw = P.nib ? P.nib_ws : (uint32_t)max_seed / epw + 1u;
-        P.off_ws = P.off_wb + wbw * nt * 4u;
-        P.lds = ((size_t)P.off_ws + (size_t)wsw * nt * 4u + 15) / 16 * 16;
-        int per_cu = (int)((160u * 1024u) / P.lds);
-        const int cap = 4 * HSA_WAVES_SIMD / (int)(nt / 64);  // 16 waves per CU
-        const int want = g_waves_per_cu / (int)(nt / 64);
-        if (per_cu > cap) per_cu = cap;
-        if (per_cu > want) per_cu = want > 0 ? want : 1;
-        return per_cu;
-    };
-    static const int force256 = getenv("HSA_WG256") != nullptr;   // A/B runs only
-    auto best = [&]() {
-        int per_cu = layout(P.huge ? 64 : 256);
-        if (per_cu < 4 && !force256 && !P.huge) {
-            const int p64 = layout(64);
-            if (p64 > per_cu * 4) per_cu = p64;
-            else per_cu = layout(256);
-        }
-        return per_cu;
-    };
-    int per_cu = best();
-    // long reads: 4-bit elements when the 8-bit rows leave the CU short of 16 waves, in
-    // ungapped searches, which are latency-bound: config 5's k_search 45.6 -> 38.4 ms.
-    // Gapped ones are issue-bound and lose more to the unpacking and the base loads
-    // than they gain in waves (config 4: 1 988 -> 2 147 ms; config 3: equal).
-    // HSA_WFMT=nib forces them where exact, =byte keeps 8-bit (tests and A/B runs).
-    const char *wf = getenv("HSA_WFMT");
-    const bool force_nib = wf && !strcmp(wf, "nib"), no_nib = wf && !strcmp(wf, "byte");
-    if (nib_ok && !wide && !P.huge && !no_nib && (force_nib || (!gaps && per_cu * (int)(P.nt / 64) < 16))) {
-        const int waves8 = per_cu * (int)(P.nt / 64);
-        const LaunchPlan keep = P;
-        P.nib = true;
-        const int per_nib = best();
-        if (!force_nib && per_nib * (int)(P.nt / 64) <= waves8) { P = keep; }
-        else per_cu = per_nib;
-    }
-    if (P.lds > 160 * 1024) { hsa_set_error("reads too long for the LDS budget (%zu bytes)", P.lds); return HSA_E_ARG; }
-    if (per_cu < 1) { hsa_set_error("search kernel does not fit (LDS %zu)", P.lds); return HSA_E_ARG; }
-    const uint32_t NTB = P.nt;
-    size_t blocks = (size_t)ix->n_cu * per_cu;
-    P.resident = blocks * NTB;
-    size_t need_blocks = ((size_t)n_jobs + NTB - 1) / NTB;
-    if (P.huge) {
-        blocks = 1;                                          // 64 lanes: a handful of reads
-    } else if (big) {
-        static const size_t big_lanes = getenv("HSA_BIG_LANES") ? strtoull(getenv("HSA_BIG_LANES"), nullptr, 10) : 4096;
-        const size_t big_blocks = big_lanes / NTB > 0 ? big_lanes / NTB : 1;
-        blocks = need_blocks < big_blocks ? need_blocks : big_blocks;
-        // the BIG pass's scratch is reserved for all its lanes whatever the pass's size:
-        // the attach-time warm-up then allocates it (7.3 GB at the default shape) instead
-        // of a process's first full batch
-        P.res_lanes = big_blocks * NTB;
-    } else if (need_blocks < blocks) {
-        blocks = need_blocks;
-    }
-    if (blocks < 1) blocks = 1;
-    P.blocks = blocks;
-    P.lanes = blocks * NTB;
-    if (getenv("HSA_VERBOSE")) {                   // read per plan: tests switch it on mid-process
-        int occ = 0;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_search<1, true, uint8_t, 256>, 256, P.lds);
-        fprintf(stderr, "[hsa] launch: %d CUs x %d workgroups of %u lanes (runtime occupancy query says %d), "
-                "LDS %zu B, %zu workgroups, %d buckets%s\n", ix->n_cu, per_cu, P.nt, occ, P.lds, blocks, nb,
-                P.nib ? ", 4-bit rows" : "");
-    }
-    // pool slots are not reused within a search: gapped searches push many more.  A
-    // deeper main-pass pool keeps the long gapped searches inside the main pass, where
-    // their tails overlap other lanes' work, instead of the serial overflow re-run:
-    // config 4 (150 bp, -o 1) 2.36 -> 2.07 s per 1M reads at 32768 (49152: same)
-    static const int pool_env = getenv("HSA_POOL_ENTRIES") ? atoi(getenv("HSA_POOL_ENTRIES")) : 0;   // A/B runs
-    const int pool_main = g_pool_entries ? g_pool_entries : pool_env > 0 && pool_env <= 65535 ? pool_env : 0;
-    // gapped reads of up to 128 bases: 16 384 (config 3 at 32 768: 106 GB of scratch per
-    // handle; at 16 384 53 GB and k_search 284.9 -> 283.7 ms, profiles/r05_pool16k_ab.log);
-    // longer gapped reads keep 32 768 (config 4 at 8 192: 32 s against 1.2 s)
-    P.pcap = big ? 65535u : (uint32_t)(pool_main ? pool_main : (gaps ? (max_len <= 128 ? 16384 : 32768) : 8192));
-    // searches of at most 32 bases (the splice path's 12-mer anchors, which run on every
-    // resident lane) keep 8 192 entries with gap opens too: 155 -> 39 GB of scratch per
-    // handle at config 4, the anchors' time unchanged (profiles/r05_pool_short_ab.log);
-    // HSA_POOL_SHORT=n sets it (0: the regime's default)
-    static const int pool_short = getenv("HSA_POOL_SHORT") ? atoi(getenv("HSA_POOL_SHORT")) : 8192;
-    if (!big && !pool_main && max_len <= 32 && pool_short > 0 && pool_short <= 65535) P.pcap = (uint32_t)pool_short;
-    P.hcap = big ? 16384u : (uint32_t)g_hit_cap;
-    if (P.huge) {
-        // live entries never exceed max_entries + 9 (bwtgap.c:150-151); the pool is
-        // capped at 4 Mi entries per lane (80 MB), beyond which a read stays unfinished
-        const uint64_t want = (uint64_t)(max_entries > 0 ? max_entries : 0) + 16u;
-        P.pcap = (uint32_t)(want < (4ull << 20) ? want : (4ull << 20));
-        P.hcap = 262144u;
-    } else if (ent_bytes > 16 && !big) {
-        // 64-bit entries are 32 bytes: the main pass's pools stay within 64 GB of HBM
-        // (next to an index of up to ~2 x 16 GB for a 15 Gbp text); reads that need
-        // more go to the big and huge passes as usual
-        const size_t budget = (size_t)64 << 30;
-        if (P.lanes * P.pcap * ent_bytes > budget) {
-            const size_t p = budget / (P.lanes * ent_bytes);
-            P.pcap = (uint32_t)(p < 1024 ? 1024 : p);
-        }
-    }
-    return 0;
-}
-
-template <typename WT, int NT, typename IT>
-static void launch_search_nt(const LaunchPlan &P, const SearchArgs &A, hipStream_t st)
-{
-    const dim3 g((unsigned)P.blocks), b(NT);
-    if (P.nb <= 32) {
-        if (P.gaps) hipLaunchKernelGGL((k_search<0, true, WT, NT, false, IT>), g, b, P.lds, st, A);
-        else hipLaunchKernelGGL((k_search<0, false, WT, NT, false, IT>), g, b, P.lds, st, A);
-    } else if (P.nb <= 64) {
-        if (P.gaps) hipLaunchKernelGGL((k_search<1, true, WT, NT, false, IT>), g, b, P.lds, st, A);
-        else hipLaunchKernelGGL((k_search<1, false, WT, NT, false, IT>), g, b, P.lds, st, A);
-    } else {
-        if (P.gaps) hipLaunchKernelGGL((k_search<2, true, WT, NT, false, IT>), g, b, P.lds, st, A);
-        else hipLaunchKernelGGL((k_search<2, false, WT, NT, false, IT>), g, b, P.lds, st, A);
-    }
-}
-
-template <typename WT, typename IT>
-static void launch_search(const LaunchPlan &P, const SearchArgs &A, hipStream_t st)
-{
-    if constexpr (!std::is_same<WT, WNib>::value) {
-        if (P.nib) {                                 // never a HUGE pass (plan_launch)
-            if (P.nt == 64) launch_search_nt<WNib, 64, IT>(P, A, st);
-            else launch_search_nt<WNib, 256, IT>(P, A, st);
-            return;
-        }
-    }
-    if (P.huge) {
-        const dim3 g((unsigned)P.blocks), b(64);
-        if (P.gaps) hipLaunchKernelGGL((k_search<2, true, WT, 64, true, IT>), g, b, P.lds, st, A);
-        else hipLaunchKernelGGL((k_search<2, false, WT, 64, true, IT>), g, b, P.lds, st, A);
-        return;
-    }
-    if (P.nt == 64) launch_search_nt<WT, 64, IT>(P, A, st);
-    else launch_search_nt<WT, 256, IT>(P, A, st);
-}
-
-// One search pass over jobs (or a job_list subset) with device pointers: k_widths
-// fills the width rows of every (read, strand), then k_search runs the reads.
-// caller-width mode of a pass (hsa_match_gap_batch)
-struct MgPass {
-    const hsa_mg_job_t *d_mg;
-    int32_t *d_cw;
-};
-
-template <typename IT = uint32_t>
-static SearchArgs pass_args(hsa_index *ix, const LaunchPlan &P, SearchScratch &S, const hsa_regime_t *d_regimes,
-                            const uint8_t *d_bmap, const hsa_job_t *d_jobs, const int32_t *d_list, int n, int max_len,
-                            int max_seed, const uint8_t *d_codes, int32_t *d_n, uint32_t *d_fl, uint64_t *d_ho,
-                            uint32_t *d_hits, uint64_t hit_cap, unsigned long long *d_ctr, const MgPass *mg)
-{
-    constexpr size_t WGB = sizeof(IT);       // bytes per full w value (wg rows)
-    const uint32_t esz = P.wide ? 2u : 1u;
-    const uint32_t rb = (((uint32_t)max_len + 1u) * esz + 3u) & ~3u, rs = (((uint32_t)max_seed + 1u) * esz + 3u) & ~3u;
-    const uint32_t rg = (uint32_t)max_len + 1u;
-    const size_t rows = ((size_t)n + 63) / 64 * 64 * 2;     // two 64-row-aligned planes (lazy widths)
-    uint8_t *wr = (uint8_t *)ix->d_wrows;
-    SearchArgs A;
-    A.fwd = RankDir{ix->blk[0], ix->isa0};
-    A.rev = RankDir{ix->blk[1], ix->risa0};
-    A.T = ix->T;
-    memcpy(A.C, ix->C, sizeof A.C);
-    A.fwd64 = hsa_rank_dir64(ix, 0);
-    A.rev64 = hsa_rank_dir64(ix, 1);
-    A.T64 = ix->T64;
-    memcpy(A.C64, ix->C64, sizeof A.C64);
-    A.regimes = d_regimes; A.bmap = d_bmap; A.jobs = d_jobs; A.job_list = d_list; A.n_jobs = n; A.codes = d_codes;
-    A.n_aln = d_n; A.flags = d_fl; A.hit_off = d_ho; A.hits = d_hits; A.hit_cap = hit_cap; A.ctr = d_ctr;
-    A.wb = wr; A.ws = wr + rows * rb; A.wg = reinterpret_cast<uint32_t *>(wr + rows * (rb + rs));
-    A.rb = rb; A.rs = rs; A.rg = rg;
-    A.pool = S.pool; A.nxt = S.nxt; A.hbuf = S.hbuf;
-    A.pcap = P.pcap; A.hcap = P.hcap;        // the planned capacities (the scratch may be larger)
-    A.nb = P.nb; A.off_heads = P.off_heads; A.off_wb = P.off_wb; A.off_ws = P.off_ws;
-    A.nib_wb = P.nib_wb; A.nib_ws = P.nib_ws;
-    A.mm_buckets = ix->staged_mmb ? 1u : 0u;
-    A.ntab = P.ntab;
-    A.batch_k = (uint32_t)g_batch_k;
-    A.batch_idle = (uint32_t)g_batch_idle;
-    A.ovf_list = nullptr; A.n_dev = nullptr; A.qctr = 0; A.ovf_ctr = 8;
-    A.split = 0; A.sp_n = nullptr; A.sp_off = nullptr; A.sp_q = nullptr; A.sp_p = nullptr;
-    const char *te = getenv("HSA_TRIE");           // HSA_TRIE=0: rank steps only (A/B runs)
-    const bool tr = ix->trie_depth > 0 && ix->trie_wide == (sizeof(IT) == 8) && !(te && atoi(te) == 0);
-    A.ktw = tr ? ix->d_trie_w : nullptr;
-    A.ktd = tr ? ix->trie_depth : 0u;
-    A.wkey = nullptr; A.perm = nullptr; A.okey = 0;
-    A.fwd_list = nullptr; A.fwd_n = nullptr; A.fwd_only = 0; A.rmap = nullptr;
-    A.fr_budget = 0; A.fr_demand = 0; A.fr_cap = 0;
-    A.fr_ent = nullptr; A.fr_tag = nullptr; A.fr_rq = nullptr; A.fr_st = nullptr; A.fr_q = nullptr; A.fr_p = nullptr; A.fr_c = nullptr;
-    A.mg = mg ? mg->d_mg : nullptr;
-    A.cw = mg ? mg->d_cw : nullptr;
-    A.wbid = mg ? reinterpret_cast<int32_t *>(wr + rows * (rb + rs + WGB * (size_t)rg)) : nullptr;
-    A.wq = reinterpret_cast<uint32_t *>(wr + rows * (rb + rs + WGB * (size_t)rg + (mg ? 4 * (size_t)rg : 0)));
-    return A;
-}
-
-// Strand-split mode for the main pass of a small batch: each read's two strands on two
-// lanes when both fit on the chip at once (HSA_SPLIT=0/1 forces it off/on).  A read's
-// search chain halves (rc and fwd side by side); the fwd strand's work is speculative, so
-// large batches, which fill every lane anyway, keep one read per lane.
-// Helpers are opt-in (HSA_HELP=1): exact, but measured slower on the drop-in's 100 000-read
-// calls ("Helpers")
-static bool use_help()
-{
-    const char *e = getenv("HSA_HELP");
-    return e && atoi(e) != 0;
-}
-
-// (helpers run in gapped 32-bit kernels only, k_search's FRH)
-template <typename IT>
-static bool help_kernel(const LaunchPlan &P) { return use_help() && HSA_HELPERS && P.gaps && sizeof(IT) == 4; }
-
-static bool use_split(const LaunchPlan &P, int n, const unsigned long long *n_dev, const MgPass *mg, uint32_t qctr,
-                      bool help)
-{
-    if (mg || n_dev || qctr != 0 || P.huge || n <= 0) return false;
-    const char *e = getenv("HSA_SPLIT");
-    if (e) return atoi(e) != 0;
-    // with helpers, also batches of up to one read per resident lane: their tails are the
-    // long strand searches the waiting lanes then share
-    return (help ? (size_t)n : 2 * (size_t)n) <= P.resident;
-}
-
-// Helpers of a strand-split pass (SearchArgs::fr_*): the shared frontier and the per-item
-// state in ix->d_help, zeroed on the pass's stream.  HSA_HELP=0: off; HSA_HELP_BUDGET pops
-// before a strand may offer its entries (default 512); HSA_HELP_DEMAND waiting lanes beyond
-// the unsearched chunks before it does (default: half the pass's lanes, so that only the
-// strands still running when half the chip waits -- the launch's tail -- offer); HSA_HELP_CAP
-// chunks of FR_CH entries (default 1 Mi: 512 MB).
-// Off when a regime's max_entries does not exceed the pool: then the main pass's stack
-// stays below the reference's max_entries break (bwtgap.c:150-151) whenever it completes,
-// and a strand its helpers answer counts the reference's rank queries and pops.
-template <typename IT>
-static int help_args(hsa_index *ix, SearchArgs &A, size_t items, const LaunchPlan &P, hipStream_t st)
-{
-    if (!help_kernel<IT>(P) || ix->staged_min_entries <= (int)P.pcap + 16) return 0;
-    auto env = [](const char *k, long d) { const char *v = getenv(k); return v ? atol(v) : d; };
-    const long budget = env("HSA_HELP_BUDGET", 512), demand = env("HSA_HELP_DEMAND", (long)(P.lanes / 2));
-    const long cap = env("HSA_HELP_CAP", 1l << 20);
-    if (budget <= 0 || cap <= 0 || cap > (1l << 24) || demand < 0 || items >= (1u << 26)) return 0;
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t o_st = 256, o_q = o_st + al(items * 4), o_p = o_q + al(items * 8), o_tag = o_p + al(items * 8);
-    const size_t o_rq = o_tag + al((size_t)cap * 4);
-    const size_t o_ent = o_rq + al((size_t)cap * 4), total = o_ent + (size_t)cap * FR_CH * FR_EW * 4;
-    int rc = hsa_grow(&ix->d_help, &ix->d_help_cap, total);
-    if (rc) return rc;
-    char *d = (char *)ix->d_help;
-    HSA_HIP(hipMemsetAsync(d, 0, o_ent, st));       // counters, item state and sums, tags, ready queue
-    A.fr_budget = (uint32_t)budget; A.fr_demand = (uint32_t)demand; A.fr_cap = (uint32_t)cap;
-    A.fr_c = (unsigned long long *)d;
-    A.fr_st = (uint32_t *)(d + o_st);
-    A.fr_q = (unsigned long long *)(d + o_q);
-    A.fr_p = (unsigned long long *)(d + o_p);
-    A.fr_tag = (uint32_t *)(d + o_tag);
-    A.fr_rq = (uint32_t *)(d + o_rq);
-    A.fr_ent = (uint32_t *)(d + o_ent);
-    return 0;
-}
-
-// The pass's search scratch (per-lane pools, links, staged hits), sized to what the
-// device can give: the pool per lane is the plan's capacity unless that would not fit in
-// the free HBM (less a 2 GiB margin) or in HSA_SCRATCH_MB, in which case it is halved
-// until it does (down to 512 entries), and again if the allocation itself fails.  A
-// smaller pool changes no result: a read that outgrows its lane is re-run in the BIG and
-// HUGE passes as before, so the cost is speed, never an error (the reference's capacity
-// bound is max_entries, bwtgap.c:150-151, which the HUGE pass keeps).
-static int scratch_fit(hsa_index *ix, SearchScratch &S, LaunchPlan &P, size_t EW)
-{
-    const size_t lb = P.huge ? 4 : 2, floor_cap = 512;
-    auto pe_of = [&](uint32_t pc) { return (size_t)((pc + 31u) & ~31u) * EW; };
-    const size_t rl = P.res_lanes > P.lanes ? P.res_lanes : P.lanes;
-    auto bytes = [&](uint32_t pc) { return rl * (pe_of(pc) * (16 + lb) + (size_t)P.hcap * EW * 36); };
-    const bool held = S.pool && lb == S.link_bytes && rl * pe_of(P.pcap) <= S.pool_entries &&
-                      rl * (size_t)P.hcap * EW <= S.hit_entries;
-    if (!held && !P.huge) {
-        const char *cm = getenv("HSA_SCRATCH_MB");      // read per pass: tests set it mid-process
-        const size_t cap_mb = cm ? strtoull(cm, nullptr, 10) : 0;
-        size_t fr = 0, tot = 0;
-        if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = (size_t)-1 / 2; }
-        fr += S.pool_entries * (16 + S.link_bytes) + S.hit_entries * 36;     // what the reservation frees first
-        size_t avail = fr > ((size_t)2 << 30) ? fr - ((size_t)2 << 30) : 0;
-        if (cap_mb && avail > (cap_mb << 20)) avail = cap_mb << 20;
-        const uint32_t want = P.pcap;
-        while (bytes(P.pcap) > avail && P.pcap > floor_cap) P.pcap = P.pcap / 2 > floor_cap ? P.pcap / 2 : floor_cap;
-        if (P.pcap != want && getenv("HSA_VERBOSE"))
-            fprintf(stderr, "[hsa] search scratch: pool %u -> %u entries per lane (%.1f GB for %zu lanes; %.1f GB "
-                            "available)\n", want, P.pcap, bytes(P.pcap) / 1e9, P.lanes, avail / 1e9);
-    }
-    for (;;) {
-        const int rc = hsa_scratch_reserve(S, rl, pe_of(P.pcap), (size_t)P.hcap * EW, lb);
-        if (rc != HSA_E_MEM || P.huge || P.pcap <= floor_cap) return rc;
-        P.pcap = P.pcap / 2 > floor_cap ? P.pcap / 2 : floor_cap;
-        if (getenv("HSA_VERBOSE")) fprintf(stderr, "[hsa] search scratch: allocation failed, pool -> %u per lane\n", P.pcap);
-    }
-}
-
-template <typename IT = uint32_t>
-static int launch_pass(hsa_index *ix, const LaunchPlan &P0, SearchScratch &S, const hsa_regime_t *d_regimes,
-                       const uint8_t *d_bmap, const hsa_job_t *d_jobs, const int32_t *d_list, int n, int max_len,
-                       int max_seed, const uint8_t *d_codes, int32_t *d_n, uint32_t *d_fl, uint64_t *d_ho,
-                       uint32_t *d_hits, uint64_t hit_cap, unsigned long long *d_ctr, hipStream_t st,
-                       int32_t *ovf_list = nullptr, const unsigned long long *n_dev = nullptr, uint32_t qctr = 0,
-                       const MgPass *mg = nullptr, uint32_t ovf_ctr = 8)
-{
-    const bool split = use_split(P0, n, n_dev, mg, qctr, help_kernel<IT>(P0));
-    LaunchPlan P = P0;
-    if (split) {                                        // lanes for 2 n items
-        const size_t need = (2 * (size_t)n + P.nt - 1) / P.nt, cap = P.resident / P.nt;
-        P.blocks = need < cap ? need : cap;
-        P.lanes = P.blocks * P.nt;
-    }
-    // 64-bit intervals: two uint4 per pool entry, 10 staged words per hit (HitW)
-    constexpr size_t EW = sizeof(IT) / 4;
-    int rc = scratch_fit(ix, S, P, EW);
-    if (rc) return rc;
-    const uint32_t esz = P.wide ? 2u : 1u;
-    const uint32_t rb = (((uint32_t)max_len + 1u) * esz + 3u) & ~3u, rs = (((uint32_t)max_seed + 1u) * esz + 3u) & ~3u;
-    const uint32_t rg = (uint32_t)max_len + 1u;
-    const size_t rows = ((size_t)n + 63) / 64 * 64 * 2;     // two 64-row-aligned planes (lazy widths)
-    const size_t row_bytes = rb + rs + sizeof(IT) * (size_t)rg + (mg ? 4 * (size_t)rg : 0);   // + full bids (caller widths)
-    // + wq (4 n), cost keys (2 n), order (4 n) and its 32 counters
-    if ((rc = hsa_grow(&ix->d_wrows, &ix->d_wrows_cap, rows * row_bytes + 10 * (size_t)n + 1024))) return rc;
-    if (mg) {
-        if constexpr (sizeof(IT) != 4) {
-            hsa_set_error("caller-width searches (bwt_match_gap) take 32-bit indexes");
-            return HSA_E_ARG;
-        } else {
-            SearchArgs A = pass_args<IT>(ix, P, S, d_regimes, d_bmap, d_jobs, d_list, n, max_len, max_seed, d_codes, d_n,
-                                         d_fl, d_ho, d_hits, hit_cap, d_ctr, mg);
-            A.ovf_list = ovf_list; A.n_dev = n_dev; A.qctr = qctr; A.ovf_ctr = ovf_ctr;
-            if (qctr == 0) HSA_HIP(hipMemsetAsync(d_ctr, 0, 16 * sizeof(unsigned long long), st));   // not on a re-run
-            const unsigned nb = (unsigned)(((size_t)n + BLOCK - 1) / BLOCK);
-            if (P.wide) hipLaunchKernelGGL(k_widths_import<uint16_t>, dim3(nb ? nb : 1), dim3(BLOCK), 0, st, A);
-            else hipLaunchKernelGGL(k_widths_import<uint8_t>, dim3(nb ? nb : 1), dim3(BLOCK), 0, st, A);
-            HSA_HIP(hipGetLastError());
-            if (ix->ev_split) HSA_HIP(hipEventRecord(ix->ev_split, st));
-            if (P.wide) launch_search<uint16_t, uint32_t>(P, A, st);
-            else launch_search<uint8_t, uint32_t>(P, A, st);
-            HSA_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_widths_export, dim3(nb ? nb : 1), dim3(BLOCK), 0, st, A);
-            HSA_HIP(hipGetLastError());
-            return 0;
-        }
-    }
-    SearchArgs A = pass_args<IT>(ix, P, S, d_regimes, d_bmap, d_jobs, d_list, n, max_len, max_seed, d_codes, d_n, d_fl,
-                                 d_ho, d_hits, hit_cap, d_ctr, nullptr);
-    A.ovf_list = ovf_list; A.n_dev = n_dev; A.qctr = qctr; A.ovf_ctr = ovf_ctr;
-    if (split) {
-        const size_t m = 2 * (size_t)n, al = (m * 8 + 255) / 256 * 256;
-        if ((rc = hsa_grow(&ix->d_split, &ix->d_split_cap, 3 * al))) return rc;
-        char *d = (char *)ix->d_split;
-        A.split = 1;
-        A.sp_off = (uint64_t *)d;
-        A.sp_n = (int32_t *)(d + al);
-        A.sp_q = (uint32_t *)(d + al + al / 2);
-        A.sp_p = (uint32_t *)(d + 2 * al);
-        if (!P.huge && (rc = help_args<IT>(ix, A, m, P, st))) return rc;
-    }
-    if (qctr == 0) HSA_HIP(hipMemsetAsync(d_ctr, 0, 16 * sizeof(unsigned long long), st));   // not on a re-run
-    // cost order: the main pass of a batch with more reads than the chip has lanes
-    // (HSA_ORDER=0/1 forbids / forces it)
-    const char *oe = getenv("HSA_ORDER");
-    const bool order = !split && !n_dev && qctr == 0 && n > 0 &&
-                       (oe ? atoi(oe) != 0 : (size_t)n > P.resident);
-    uint32_t *d_oh = nullptr;
-    if (order) {
-        char *tail = (char *)A.wq + 4 * (size_t)n;
-        A.wkey = (uint8_t *)tail;
-        // the tail-length key: config 2 k_search 18.5-18.9 -> 17.9-18.0 ms, config 3 and 5 1-2 %
-        // (profiles/r03_ab2_okey_*); HSA_ORDER_KEY=0: the final bid alone
-        static const uint32_t okey = getenv("HSA_ORDER_KEY") ? (uint32_t)atoi(getenv("HSA_ORDER_KEY")) : 1u;
-        A.okey = okey;
-        const size_t ko = (2 * (size_t)n + 15) / 16 * 16;
-        d_oh = (uint32_t *)(tail + ko);
-        HSA_HIP(hipMemsetAsync(d_oh, 0, 32 * 4, st));
-    }
-    // lazy forward rows: the main pass of a batch searched one read per lane computes a
-    // read's forward row only when its rc search cannot hit; the reads whose rc search
-    // finds nothing without one get it in the forward pass below.  It pays for long reads
-    // (config 5's 250 bp: k_widths 17.0 -> 15.7 ms); for 100 bp reads the second width
-    // launch costs more than the rows it saves (5.25 -> 5.68 ms), so by default reads of
-    // 200 bases or more (HSA_LAZY=0 / 1 forbids / forces it)
-    const char *le = getenv("HSA_LAZY");
-    const bool lazy = !split && !n_dev && qctr == 0 && n > 0 && (le ? atoi(le) != 0 : max_len >= 200);
-    unsigned long long *d_fwd_n = nullptr;
-    int32_t *d_list2 = nullptr;
-    unsigned long long *d_n2 = nullptr;
-    if (lazy) {
-        // [count, count2 | forward-pass list (n) | list2 (n)]
-        if ((rc = hsa_grow(&ix->d_fwd, &ix->d_fwd_cap, 512 + 12 * (size_t)n))) return rc;
-        d_fwd_n = (unsigned long long *)ix->d_fwd;
-        d_n2 = d_fwd_n + 1;
-        HSA_HIP(hipMemsetAsync(d_fwd_n, 0, 16, st));
-        A.fwd_n = d_fwd_n;
-        A.fwd_list = (int32_t *)((char *)ix->d_fwd + 128);
-        d_list2 = A.fwd_list + ((size_t)n + 31) / 32 * 32;
-        A.rmap = d_list2 + ((size_t)n + 31) / 32 * 32;
-    }
-    if (lazy) {
-        const unsigned rblocks = (unsigned)(((size_t)n + BLOCK - 1) / BLOCK);
-        if (P.wide) {
-            hipLaunchKernelGGL((k_widths_reads<uint16_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, A, 1u, d_list2, d_n2);
-            hipLaunchKernelGGL((k_widths_reads<uint16_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, A, 3u, d_list2, d_n2);
-        } else {
-            hipLaunchKernelGGL((k_widths_reads<uint8_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, A, 1u, d_list2, d_n2);
-            hipLaunchKernelGGL((k_widths_reads<uint8_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, A, 3u, d_list2, d_n2);
-        }
-    } else {
-        size_t wblocks = ((size_t)n * 2 + BLOCK - 1) / BLOCK;
-        if (wblocks < 1) wblocks = 1;
-        if (P.wide) hipLaunchKernelGGL((k_widths<uint16_t, IT>), dim3((unsigned)wblocks), dim3(BLOCK), 0, st, A);
-        else hipLaunchKernelGGL((k_widths<uint8_t, IT>), dim3((unsigned)wblocks), dim3(BLOCK), 0, st, A);
-    }
-    HSA_HIP(hipGetLastError());
-    if (order) {
-        int32_t *d_perm = (int32_t *)(d_oh + 32);
-        const unsigned nb = (unsigned)(((size_t)n + BLOCK - 1) / BLOCK);
-        hipLaunchKernelGGL(k_order_hist, dim3(nb), dim3(BLOCK), 0, st, A, d_oh);
-        hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(1), 0, st, d_oh);
-        hipLaunchKernelGGL(k_order_scatter, dim3(nb), dim3(BLOCK), 0, st, A, d_oh, d_perm);
-        HSA_HIP(hipGetLastError());
-        A.perm = d_perm;
-    }
-    if (ix->ev_split && qctr == 0) HSA_HIP(hipEventRecord(ix->ev_split, st));   // the main pass only
-    if (P.wide) launch_search<uint16_t, IT>(P, A, st);
-    else launch_search<uint8_t, IT>(P, A, st);
-    HSA_HIP(hipGetLastError());
-    if (lazy) {
-        // the forward pass: the forward rows and the forward-strand searches of the reads
-        // the main pass listed (count on the device; queue head ctr[6]); its overflows go
-        // to the same re-run list as the main pass's
-        SearchArgs F = A;
-        F.job_list = A.fwd_list; F.n_dev = d_fwd_n; F.qctr = 6; F.fwd_only = 1;
-        F.fwd_list = nullptr; F.fwd_n = nullptr; F.wkey = nullptr; F.perm = nullptr; F.rmap = nullptr;
-        const unsigned rblocks = (unsigned)(((size_t)n + BLOCK - 1) / BLOCK);
-        if (P.wide) hipLaunchKernelGGL((k_widths_reads<uint16_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, F, 2u, d_list2, d_n2);
-        else hipLaunchKernelGGL((k_widths_reads<uint8_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, F, 2u, d_list2, d_n2);
-        HSA_HIP(hipGetLastError());
-        if (P.wide) launch_search<uint16_t, IT>(P, F, st);
-        else launch_search<uint8_t, IT>(P, F, st);
-        HSA_HIP(hipGetLastError());
-    }
-    if (split) {
-        const unsigned nb = (unsigned)(((size_t)n + BLOCK - 1) / BLOCK);
-        hipLaunchKernelGGL(k_split_finalize, dim3(nb), dim3(BLOCK), 0, st, A);
-        HSA_HIP(hipGetLastError());
-        if (getenv("HSA_VERBOSE")) {
-            fprintf(stderr, "[hsa] strand-split main pass: %d reads on %zu lanes\n", n, P.lanes);
-            if (A.fr_c) {
-                unsigned long long c[9];
-                HSA_HIP(hipMemcpyAsync(c, A.fr_c, sizeof c, hipMemcpyDeviceToHost, st));
-                HSA_HIP(hipStreamSynchronize(st));
-                fprintf(stderr, "[hsa] helpers: %llu offers (%llu refused), %llu chunks, %llu sub-searches, %llu strands "
-                                "answered by them, %llu rank queries in sub-searches\n", c[4], c[5], c[0], c[6], c[7], c[8]);
-            }
-        }
-    }
-    return 0;
-}
-
-static bool any_gaps(const hsa_regime_t *rg, int n)
-{
-    for (int r = 0; r < n; ++r)
-        if (rg[r].max_gapo > 0) return true;
-    return false;
-}
-
-// 16-bit pruning elements when a bid may be compared with a bound above 14 (WFmt).
-static bool need_wide(const hsa_regime_t *rg, int n)
-{
-    for (int r = 0; r < n; ++r)
-        if (rg[r].max_diff > 14 || rg[r].max_seed_diff > 14) return true;
-    return false;
-}
-
-// 4-bit pruning elements are exact while every bid comparison bound is <= 6 (WFmt<WNib>);
-// a job's max_diff never exceeds its regime's
-static bool nib_exact(const hsa_regime_t *rg, int n)
-{
-    for (int r = 0; r < n; ++r)
-        if (rg[r].max_diff > 6 || rg[r].max_seed_diff > 6) return false;
-    return true;
-}
-
-static int jobs_limits(const hsa_job_t *jobs, int n, int &max_len, int &max_seed)
-{
-    max_len = 0; max_seed = 0;
-    for (int j = 0; j < n; ++j) {
-        if (jobs[j].len > ANY_MAX_LEN) { hsa_set_error("read %d longer than %d (gap_entry_t.info, bwtgap.c:157)", j, ANY_MAX_LEN); return HSA_E_ARG; }
-        if (jobs[j].max_diff < -1) { hsa_set_error("max_diff out of range"); return HSA_E_ARG; }
-        if ((int)jobs[j].len > max_len) max_len = (int)jobs[j].len;
-        if ((int)jobs[j].len > jobs[j].seed_len && jobs[j].seed_len > max_seed) max_seed = jobs[j].seed_len;
-    }
-    return 0;
-}
-
-// regimes + bucket maps into the staging area: [regimes (256 B)][bmap 2*MAXS].
-// Repeated launches with the same options skip the copy (a pageable H2D copy
-// would otherwise wait for the stream and stall the host between launches).
-static int stage_regimes(hsa_index *ix, const hsa_regime_t *regimes, int n_regimes, char *dst, int &nb,
-                         hipStream_t st, bool force)
-{
-    static_assert(256 + 2 * MAXS <= sizeof(ix->staged), "staging copy");
-    uint8_t host[256 + 2 * MAXS];
-    memset(host, 0xFF, sizeof host);
-    memcpy(host, regimes, sizeof(hsa_regime_t) * n_regimes);
-    nb = 1;
-    int ntab = 8;
-    for (int r = 0; r < n_regimes; ++r) {
-        int k = bucket_map(regimes[r], host + 256 + r * MAXS);
-        nb = k > nb ? k : nb;
-        ntab = regimes[r].n_stacks > ntab ? regimes[r].n_stacks : ntab;
-    }
-    if (nb > MAXB) { hsa_set_error("%d reachable scores: at most %d stack buckets", nb, MAXB); return HSA_E_ARG; }
-    ix->staged_ntab = (ntab + 7) / 8 * 8;
-    ix->staged_mmb = mm_buckets(regimes, n_regimes, host + 256);
-    ix->staged_min_entries = regimes[0].max_entries;
-    for (int r = 1; r < n_regimes; ++r)
-        if (regimes[r].max_entries < ix->staged_min_entries) ix->staged_min_entries = regimes[r].max_entries;
-    if (!force && ix->staged_valid && memcmp(ix->staged, host, sizeof host) == 0) return 0;
-    memcpy(ix->staged, host, sizeof host);
-    ix->staged_valid = 1;
-    HSA_HIP(hipMemcpyAsync(dst, ix->staged, sizeof host, hipMemcpyHostToDevice, st));
-    HSA_HIP(hipStreamSynchronize(st));
-    return 0;
-}
-
-// ---------------------------------------------------------------- the k_search_any passes
-// Device buffers of one search's k_search_any passes (in ix->d_any_aux): the regimes, the
-// counters (0 jobs for k_search, 1 jobs for k_search_any, 2 its queue head, 3 jobs it
-// hands to its large-capacity pass, 4 that pass's queue head) and the job lists.
-struct AnyBufs {
-    hsa_regime_t *reg;
-    unsigned long long *cnt;
-    int32_t *l_fast, *l_any, *l_ovf;
-};
-
-static int any_prepare(hsa_index *ix, const hsa_regime_t *regimes, int n_regimes, size_t n, hipStream_t st, AnyBufs &B)
-{
-    const size_t lb = (n * 4 + 255) / 256 * 256;
-    if (ix->d_any_cap > ((size_t)8 << 30)) {       // a past large pass's stacks: give them back
-        HSA_HIP(hipStreamSynchronize(st));
-        (void)hipFree(ix->d_any);
-        ix->d_any = nullptr;
-        ix->d_any_cap = 0;
-    }
-    int rc = hsa_grow(&ix->d_any_aux, &ix->d_any_aux_cap, 512 + 3 * lb);
-    if (rc) return rc;
-    char *d = (char *)ix->d_any_aux;
-    B.reg = (hsa_regime_t *)d;
-    B.cnt = (unsigned long long *)(d + 256);
-    B.l_fast = (int32_t *)(d + 512);
-    B.l_any = (int32_t *)(d + 512 + lb);
-    B.l_ovf = (int32_t *)(d + 512 + 2 * lb);
-    HSA_HIP(hipMemcpyAsync(B.reg, regimes, sizeof(hsa_regime_t) * n_regimes, hipMemcpyHostToDevice, st));
-    HSA_HIP(hipMemsetAsync(B.cnt, 0, 64, st));
-    HSA_HIP(hipStreamSynchronize(st));
-    return 0;
-}
 
 // jobs up to fast_max bases go to k_search's list, longer ones to k_search_any's
 static __global__ void __launch_bounds__(BLOCK) k_partition(const hsa_job_t *jobs, int n, uint32_t fast_max,
@@ -2521,175 +1838,4 @@ static __global__ void __launch_bounds__(BLOCK) k_partition(const hsa_job_t *job
     if (j >= n) return;
     if (jobs[j].len <= fast_max) l_fast[atomicAdd(&cnt[0], 1ull)] = j;
     else l_any[atomicAdd(&cnt[1], 1ull)] = j;
-}
-
-// One k_search_any pass.  big: the large-capacity pass (pools up to the reference's
-// max_entries bound, 262 144 hits, few lanes) for the jobs the first pass overflowed.
-template <typename IT>
-static int any_pass(hsa_index *ix, const AnyBufs &B, const hsa_regime_t *regimes, int n_regimes, const hsa_job_t *d_jobs,
-                    const int32_t *d_list, const unsigned long long *n_dev, int n_host, size_t n_bound, uint32_t max_len,
-                    uint32_t max_seed, const uint8_t *d_codes, const MgPass *mg, int32_t *d_n, uint32_t *d_fl,
-                    uint64_t *d_ho, uint32_t *d_hits, uint64_t hit_cap, unsigned long long *d_ctr,
-                    unsigned long long *qhead, int32_t *ovf_list, unsigned long long *ovf_n, bool big, hipStream_t st)
-{
-    if (n_bound == 0) return 0;
-    if (big && n_dev) {
-        // the large pass's lanes hold whole stacks: size it by the reads that overflowed
-        // (one stream sync; this path only runs for reads/regimes k_search cannot hold)
-        unsigned long long cnt = 0;
-        HSA_HIP(hipMemcpyAsync(&cnt, n_dev, sizeof cnt, hipMemcpyDeviceToHost, st));
-        HSA_HIP(hipStreamSynchronize(st));
-        if (cnt == 0) return 0;
-        n_bound = (size_t)cnt;
-    }
-    AnyArgs A;
-    memset(&A, 0, sizeof A);
-    A.fwd = RankDir{ix->blk[0], ix->isa0};
-    A.rev = RankDir{ix->blk[1], ix->risa0};
-    A.fwd64 = hsa_rank_dir64(ix, 0);
-    A.rev64 = hsa_rank_dir64(ix, 1);
-    A.T = ix->T; A.T64 = ix->T64;
-    memcpy(A.C, ix->C, sizeof A.C);
-    memcpy(A.C64, ix->C64, sizeof A.C64);
-    A.regimes = B.reg; A.jobs = d_jobs; A.list = d_list; A.n_dev = n_dev; A.n_host = n_host; A.codes = d_codes;
-    A.mg = mg ? mg->d_mg : nullptr; A.cw = mg ? mg->d_cw : nullptr;
-    A.n_aln = d_n; A.flags = d_fl; A.hit_off = d_ho; A.hits = d_hits; A.hit_cap = hit_cap; A.ctr = d_ctr;
-    A.qhead = qhead; A.ovf_list = ovf_list; A.ovf_n = ovf_n;
-    uint32_t nst = 1, max_entries = 0;
-    for (int r = 0; r < n_regimes; ++r) {
-        nst = (uint32_t)regimes[r].n_stacks > nst ? (uint32_t)regimes[r].n_stacks : nst;
-        max_entries = (uint32_t)regimes[r].max_entries > max_entries ? (uint32_t)regimes[r].max_entries : max_entries;
-    }
-    // capacities: live entries never exceed max_entries + 9 (bwtgap.c:150-151)
-    const uint64_t want = (uint64_t)max_entries + 16u;
-    static const uint32_t pcap1 = getenv("HSA_ANY_PCAP") ? (uint32_t)atoi(getenv("HSA_ANY_PCAP")) : 8192u;   // A/B only
-    const uint32_t pcap = big ? (uint32_t)(want < (4ull << 20) ? want : (4ull << 20)) : pcap1;
-    const uint32_t hcap = big ? 262144u : 512u;
-    const size_t lb = any_layout<IT>(A, max_len, max_seed, nst, pcap, hcap, 10);
-    // the large pass holds whole stacks (~75 MB a lane at max_entries 2 000 000) and its
-    // reads are the slow ones: as many lanes as half the free HBM allows, up to 64 GB
-    size_t budget = (size_t)4 << 30, lanes_max = 16384;
-    if (big) {
-        size_t fr = 0, tot = 0;
-        HSA_HIP(hipMemGetInfo(&fr, &tot));
-        budget = fr / 2 < ((size_t)64 << 30) ? fr / 2 : ((size_t)64 << 30);
-        lanes_max = 4096;
-    }
-    size_t lanes = n_bound < lanes_max ? n_bound : lanes_max;
-    if (lanes * lb > budget) lanes = budget / lb;
-    if (lanes < 1) lanes = 1;
-    A.nlanes = (uint32_t)lanes;
-    if (lanes * lb + 256 > ix->d_any_cap) HSA_HIP(hipStreamSynchronize(st));   // a pass may still use the old one
-    int rc = hsa_grow(&ix->d_any, &ix->d_any_cap, lanes * lb + 256);
-    if (rc) return rc;
-    A.scratch = (uint8_t *)ix->d_any;
-    if (getenv("HSA_VERBOSE"))
-        fprintf(stderr, "[hsa] k_search_any%s: %zu lanes x %zu B (pool %u, hits %u, %u stacks, reads <= %u bp)\n",
-                big ? " (large pass)" : "", lanes, lb, pcap, hcap, nst, max_len);
-    hipLaunchKernelGGL(k_search_any<IT>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, A);
-    HSA_HIP(hipGetLastError());
-    return 0;
-}
-
-// hsa_search_device / hsa_search_device64: the main pass over a device-resident batch,
-// then the BIG and HUGE capacity re-runs, all queued on one stream without a host sync.
-template <typename IT>
-static int search_device_impl(hsa_index_t *ix, const hsa_regime_t *regimes, int n_regimes, const hsa_device_batch_t *b,
-                              void *stream)
-{
-    // regimes: host array; staged into the index's staging area
-    if (n_regimes < 1 || n_regimes > 2) { hsa_set_error("1 or 2 regimes"); return HSA_E_ARG; }
-    if (sizeof(IT) == 8 && !ix->wide) { hsa_set_error("not a 64-bit index (hsa_index_create_device64)"); return HSA_E_ARG; }
-    int rc = check_regimes(regimes, n_regimes);
-    if (rc) return rc;
-    if (b->max_len < 1 || b->max_len > ANY_MAX_LEN || b->max_seed < 0 || b->max_seed > ANY_MAX_LEN) {
-        hsa_set_error("max_len/max_seed out of range");
-        return HSA_E_ARG;
-    }
-    HSA_HIP(hipSetDevice(ix->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ix->stream;
-    unsigned long long *ctr = (unsigned long long *)b->d_counters;
-    hipEvent_t *pe = ix->pev[ix->pev_n % hsa_index::PASS_RING];
-    for (int j = 0; j < 3; ++j)
-        if (!pe[j]) HSA_HIP(hipEventCreate(&pe[j]));
-    // reads longer than k_search holds, or a regime outside its layouts: k_search_any
-    // (all jobs for such a regime; the long ones, partitioned on the device, otherwise)
-    const bool fast_rg = fast_regimes(regimes, n_regimes);
-    const bool any_path = !fast_rg || (uint32_t)b->max_len > FAST_MAX_LEN;
-    AnyBufs AB{};
-    if (any_path && (rc = any_prepare(ix, regimes, n_regimes, (size_t)b->n_jobs, st, AB))) return rc;
-    if (!fast_rg) {
-        ++ix->pev_n;
-        HSA_HIP(hipEventRecord(pe[0], st));
-        HSA_HIP(hipEventRecord(pe[1], st));
-        HSA_HIP(hipMemsetAsync(ctr, 0, 16 * sizeof(unsigned long long), st));
-        if ((rc = any_pass<IT>(ix, AB, regimes, n_regimes, b->d_jobs, nullptr, nullptr, b->n_jobs, (size_t)b->n_jobs,
-                               (uint32_t)b->max_len, (uint32_t)b->max_seed, b->d_codes, nullptr, b->d_n_aln, b->d_flags,
-                               b->d_hit_off, b->d_hits, b->hit_cap, ctr, AB.cnt + 2, AB.l_ovf, AB.cnt + 3, false, st)) ||
-            (rc = any_pass<IT>(ix, AB, regimes, n_regimes, b->d_jobs, AB.l_ovf, AB.cnt + 3, 0, (size_t)b->n_jobs,
-                               (uint32_t)b->max_len, (uint32_t)b->max_seed, b->d_codes, nullptr, b->d_n_aln, b->d_flags,
-                               b->d_hit_off, b->d_hits, b->hit_cap, ctr, AB.cnt + 4, nullptr, nullptr, true, st)))
-            return rc;
-        HSA_HIP(hipEventRecord(pe[2], st));
-        return 0;
-    }
-    const int fast_len = (uint32_t)b->max_len > FAST_MAX_LEN ? (int)FAST_MAX_LEN : b->max_len;
-    const int fast_seed = b->max_seed > fast_len ? fast_len : b->max_seed;
-    void *before = ix->d_in;
-    if ((rc = hsa_grow(&ix->d_in, &ix->d_in_cap, 1536))) return rc;
-    int nb = 0;
-    if ((rc = stage_regimes(ix, regimes, n_regimes, (char *)ix->d_in, nb, st, before != ix->d_in))) return rc;
-    LaunchPlan P, B, H;
-    constexpr uint32_t EB = 4u * sizeof(IT);        // pool entry bytes
-    const bool gaps = any_gaps(regimes, n_regimes), wide = need_wide(regimes, n_regimes);
-    int max_entries = 0;
-    for (int r = 0; r < n_regimes; ++r) max_entries = regimes[r].max_entries > max_entries ? regimes[r].max_entries : max_entries;
-    const bool nib_ok = nib_exact(regimes, n_regimes);
-    if ((rc = plan_launch(ix, b->n_jobs, fast_len, fast_seed, nb, gaps, wide, PASS_MAIN, P, 0, EB, nib_ok)) ||
-        (rc = plan_launch(ix, b->n_jobs, fast_len, fast_seed, nb, gaps, wide, PASS_BIG, B, 0, EB, nib_ok)) ||
-        (rc = plan_launch(ix, b->n_jobs, fast_len, fast_seed, nb, gaps, wide, PASS_HUGE, H, max_entries, EB)))
-        return rc;
-    if ((rc = hsa_grow(&ix->d_ovf, &ix->d_ovf_cap, (size_t)b->n_jobs * 4 + 64)) ||
-        (rc = hsa_grow(&ix->d_ovf2, &ix->d_ovf2_cap, (size_t)b->n_jobs * 4 + 64)))
-        return rc;
-    const hsa_regime_t *d_reg = (const hsa_regime_t *)ix->d_in;
-    const uint8_t *d_bmap = (const uint8_t *)ix->d_in + 256;
-    ++ix->pev_n;
-    ix->ev_split = pe[1];
-    HSA_HIP(hipEventRecord(pe[0], st));
-    const int32_t *fast_list = nullptr;
-    const unsigned long long *fast_n = nullptr;
-    if (any_path) {                                  // long reads in the batch: split it on the device
-        const unsigned g = (unsigned)(((size_t)b->n_jobs + BLOCK - 1) / BLOCK);
-        hipLaunchKernelGGL(k_partition, dim3(g ? g : 1), dim3(BLOCK), 0, st, b->d_jobs, b->n_jobs, FAST_MAX_LEN, AB.l_fast,
-                           AB.l_any, AB.cnt);
-        HSA_HIP(hipGetLastError());
-        fast_list = AB.l_fast;
-        fast_n = AB.cnt;
-    }
-    if ((rc = launch_pass<IT>(ix, P, ix->main, d_reg, d_bmap, b->d_jobs, fast_list, b->n_jobs, fast_len, fast_seed,
-                              b->d_codes, b->d_n_aln, b->d_flags, b->d_hit_off, b->d_hits, b->hit_cap, ctr, st,
-                              (int32_t *)ix->d_ovf, fast_n)))
-        return rc;
-    // exact re-runs of the reads that overflowed their lane's capacity: BIG for the
-    // main pass's (count ctr[8]), HUGE for BIG's (count ctr[12]); the read counts stay
-    // on the device, so an empty re-run is a launch whose lanes exit at once
-    if ((rc = launch_pass<IT>(ix, B, ix->big, d_reg, d_bmap, b->d_jobs, (const int32_t *)ix->d_ovf, b->n_jobs,
-                              fast_len, fast_seed, b->d_codes, b->d_n_aln, b->d_flags, b->d_hit_off, b->d_hits,
-                              b->hit_cap, ctr, st, (int32_t *)ix->d_ovf2, ctr + 8, 9, nullptr, 12)) ||
-        (rc = launch_pass<IT>(ix, H, ix->huge, d_reg, d_bmap, b->d_jobs, (const int32_t *)ix->d_ovf2, b->n_jobs,
-                              fast_len, fast_seed, b->d_codes, b->d_n_aln, b->d_flags, b->d_hit_off, b->d_hits,
-                              b->hit_cap, ctr, st, nullptr, ctr + 12, 15)))
-        return rc;
-    if (any_path &&
-        ((rc = any_pass<IT>(ix, AB, regimes, n_regimes, b->d_jobs, AB.l_any, AB.cnt + 1, 0, (size_t)b->n_jobs,
-                            (uint32_t)b->max_len, (uint32_t)b->max_seed, b->d_codes, nullptr, b->d_n_aln, b->d_flags,
-                            b->d_hit_off, b->d_hits, b->hit_cap, ctr, AB.cnt + 2, AB.l_ovf, AB.cnt + 3, false, st)) ||
-         (rc = any_pass<IT>(ix, AB, regimes, n_regimes, b->d_jobs, AB.l_ovf, AB.cnt + 3, 0, (size_t)b->n_jobs,
-                            (uint32_t)b->max_len, (uint32_t)b->max_seed, b->d_codes, nullptr, b->d_n_aln, b->d_flags,
-                            b->d_hit_off, b->d_hits, b->hit_cap, ctr, AB.cnt + 4, nullptr, nullptr, true, st))))
-        return rc;
-    HSA_HIP(hipEventRecord(pe[2], st));
-    ix->ev_split = ix->evm;
-    return 0;
 }

@@ -134,14 +134,11 @@ def test_dropin_both_entry_points_sam_identical(name, reads):
         pytest.fail(f"SAM differs: {len(got)} vs {len(ref)} lines; first differences {diff}")
 
 
-def test_splice_seeds_device_match_oracle(tiny):
-    """hsa_splice_seeds_device: after a device main pass over the splice read set
-    (-n 4 -o 1, steady state), the six seed searches of every fallback read -- prefix
-    widths, calls and searches all on the device -- equal the restated bwt_match_gap on
-    the calls hsa_amd/splice.py builds (which test_splice_seeds.py pins to the
-    reference's own seed calls)."""
+def _splice_seeds_device_run(tiny, pool_entries=0):
+    """The check of test_splice_seeds_device_match_oracle; pool_entries: the main-pass pool
+    per lane during the seed call alone.  Returns the seed call's counters."""
     import torch
-    from hsa_amd import splice
+    from hsa_amd import _lib, splice
     from hsa_amd._lib import JOB_DTYPE, DeviceBatch, SeedBatch, pad_codes, regime_of
     from oracle_ctypes import Opt, OracleIndex, default_opt
     from test_splice_seeds import read_fastq
@@ -184,8 +181,14 @@ def test_splice_seeds_device_match_oracle(tiny):
     sb = SeedBatch(d_jobs=d_jobs.data_ptr(), n_jobs=n, d_codes=d_codes.data_ptr(), d_flags=m["f"].data_ptr(),
                    d_n_aln=sn.data_ptr(), d_hit_off=so_.data_ptr(), d_hits=sh.data_ptr(), hit_cap=cap,
                    d_counters=sc.data_ptr(), max_len=int(lens.max()))
-    tiny.splice_seeds_device(srg, sb)
-    torch.cuda.synchronize()
+    if pool_entries:
+        _lib.configure(pool_entries=pool_entries)
+    try:
+        tiny.splice_seeds_device(srg, sb)
+        torch.cuda.synchronize()
+    finally:
+        if pool_entries:
+            _lib.configure(pool_entries=-1)
     g_n = sn.cpu().numpy()
     g_o = so_.cpu().numpy()
     g_h = sh.cpu().numpy().view(np.uint32).reshape(-1, 9)
@@ -215,3 +218,22 @@ def test_splice_seeds_device_match_oracle(tiny):
         bad += not np.array_equal(got, exp)
     assert bad == 0, f"{bad} of {len(hb['calls'])} seed calls differ"
     assert int(sc[7].item()) > 0     # prefix-width rank queries were counted
+    return sc.cpu().numpy()
+
+
+def test_splice_seeds_device_match_oracle(tiny):
+    """hsa_splice_seeds_device: after a device main pass over the splice read set
+    (-n 4 -o 1, steady state), the six seed searches of every fallback read -- prefix
+    widths, calls and searches all on the device -- equal the restated bwt_match_gap on
+    the calls hsa_amd/splice.py builds (which test_splice_seeds.py pins to the
+    reference's own seed calls)."""
+    _splice_seeds_device_run(tiny)
+
+
+def test_splice_seeds_device_rerun_is_exact(tiny):
+    """The same seed calls with 8 pool entries per main-pass lane: the calls that overflow
+    them go through the device's re-run passes (count in counters[8]), none is left
+    unfinished (counters[11]) and every call still equals the oracle's."""
+    c = _splice_seeds_device_run(tiny, pool_entries=8)
+    assert c[8] > 0, c[8]
+    assert c[11] == 0, "seed calls left unfinished after the re-run"

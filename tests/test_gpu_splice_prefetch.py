@@ -36,8 +36,8 @@ def fastq_codes(path):
     return [NT4[np.frombuffer(lines[i + 1].encode(), np.uint8)] for i in range(0, len(lines) - 3, 4)]
 
 
-@pytest.mark.parametrize("args", ["-n 4 -o 1", "-n 4 -o 0", "-n 2 -o 1 -e 3"])
-def test_splice_prefetch_matches_oracle(args):
+def _prefetch_check(args, pool_entries=0):
+    from hsa_amd import _lib
     from hsa_amd._lib import GpuIndex, regime_of
     from oracle_ctypes import Opt, OracleIndex, default_opt
     man = json.load(open(os.path.join(GOLD, "manifest_dropin.json")))
@@ -56,8 +56,14 @@ def test_splice_prefetch_matches_oracle(args):
     rng = np.random.default_rng(3)
     amd = rng.integers(0, od["max_diff"] + 1, len(reads)).astype(np.int32)    # per-read max_diff (bwtaln.c:330)
     lens = np.array([len(r) for r in reads], np.uint32)
-    got = gi.splice_prefetch(regime_of(so, n_stacks, so["max_diff"]), regime_of(ao, n_stacks, od["max_diff"]),
-                             lens, np.concatenate(reads), amd)
+    if pool_entries:
+        _lib.configure(pool_entries=pool_entries)
+    try:
+        got = gi.splice_prefetch(regime_of(so, n_stacks, so["max_diff"]), regime_of(ao, n_stacks, od["max_diff"]),
+                                 lens, np.concatenate(reads), amd)
+    finally:
+        if pool_entries:
+            _lib.configure(pool_entries=-1)
     gi.close()
     n_calls = {"seed": 0, "anchor": 0, "hits": 0, "sa": 0}
     for r, seq in enumerate(reads):
@@ -102,3 +108,15 @@ def test_splice_prefetch_matches_oracle(args):
                 assert np.array_equal(got["sa"][s0:s0 + len(idx)], ox.sa_positions(sa, blocks, idx)), (r, c, "SA")
                 n_calls["sa"] += len(idx)
     assert n_calls["anchor"] > 0 and n_calls["hits"] > 0 and n_calls["sa"] > 0, n_calls
+
+
+@pytest.mark.parametrize("args", ["-n 4 -o 1", "-n 4 -o 0", "-n 2 -o 1 -e 3"])
+def test_splice_prefetch_matches_oracle(args):
+    _prefetch_check(args)
+
+
+def test_splice_prefetch_rerun_is_exact():
+    """16 pool entries per main-pass lane (as test_match_gap_overflow_rerun_is_exact): the
+    seed and anchor calls that overflow them take the device's re-run passes, and every
+    answer still equals the oracle's."""
+    _prefetch_check("-n 4 -o 1", pool_entries=16)
