@@ -138,12 +138,12 @@ int hsa_need_unshared(const hsa_index *ix, const char *what);
 int hsa_grow(void **p, size_t *cap, size_t need);
 int hsa_realloc_device(void **out, void **old, size_t bytes);
 // hsa_mg_job_t.ws_off of an HSA_SEED_ALIAS job whose width_back is the first len entries
-// of a longer row (internal: the splice seeds, hsa_search.hip): terminal computed, no export
+// of a longer row (internal: the splice seeds, hsa_splice_prefetch.h): terminal computed, no export
 #define HSA_MG_PREFIX 0xFFFFFFFFFFFFFFFFull
 SaView hsa_sa_view(const hsa_index *ix);
 
-// The splice prefetch's device outputs (hsa_splice_prefetch_batch, hsa_search.hip), as
-// the splice path's kernel reads them (hsa_splice.hip).
+// The splice prefetch's device outputs (pf_dev, hsa_splice_prefetch.h), as the splice
+// path's kernel reads them (hsa_splice.hip).
 struct PfDev {
     uint32_t n, max_len, sc, rs, cws;
     const uint32_t *lens;

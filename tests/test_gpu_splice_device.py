@@ -184,3 +184,52 @@ def test_device_batch_bounds_and_scratch_release():
         if n_out != na or not np.array_equal(res[k, 2:2 + 9 * n_out].reshape(-1, 9), h):
             bad += 1
     assert bad == 0 and answered >= 0.95 * (len(sub) - 2)
+
+
+def test_host_and_device_entry_points_agree():
+    """hsa_splice_match_batch (reads from the host) and hsa_splice_device (a device batch,
+    every job flagged HSA_F_FALLBACK with n_aln 0, max_len the longest read: the strides
+    of the host path) run one prefetch over one layout of its device buffer: every read's
+    status and n_aln are the same on both, and so are an answered read's hit words.  Over
+    every read of the fixture of at least 3 bases, then over a batch of the first one
+    alone, where every region of the buffer is a few bytes."""
+    import torch
+
+    from hsa_amd._lib import JOB_DTYPE, SP_RES_WORDS, SpliceBatch, pad_codes
+    from oracle_ctypes import default_opt
+    man = json.load(open(os.path.join(GOLD, "manifest_dropin.json")))
+    reads = [r for r in fastq_codes(os.path.join(GOLD, man["splice_reads"])) if len(r) >= 3]
+    od = parse_opts(["-n", "4", "-o", "1"], default_opt())
+    srg, arg, erg = regimes(od)
+    gi = device_index(INDEX[man["index"]])
+    spliced = []                                    # per batch: answered reads with hits
+    for sub in (reads, reads[:1]):
+        n = len(sub)
+        lens = np.array([len(r) for r in sub], np.uint32)
+        host, _ = gi.splice_match(srg, arg, erg, lens, np.concatenate(sub), np.full(n, od["max_diff"], np.int32))
+        jobs = np.zeros(n, JOB_DTYPE)
+        jobs["off"] = np.concatenate([[0], np.cumsum(lens.astype(np.uint64))[:-1]])
+        jobs["len"] = lens
+        jobs["max_diff"] = od["max_diff"]
+        jobs["seed_len"] = od["seed_len"]
+        d_jobs = torch.from_numpy(jobs.view(np.uint8).copy()).cuda()
+        d_codes = torch.from_numpy(pad_codes(np.concatenate(sub))).cuda()
+        d_flags = torch.ones(n, dtype=torch.int32, device="cuda")             # HSA_F_FALLBACK
+        d_n = torch.zeros(n, dtype=torch.int32, device="cuda")
+        d_res = torch.full((n * SP_RES_WORDS,), -1, dtype=torch.int32, device="cuda")
+        d_ctr = torch.zeros(8, dtype=torch.int64, device="cuda")
+        gi.splice_device(srg, arg, erg, SpliceBatch(
+            d_jobs=d_jobs.data_ptr(), n_jobs=n, d_codes=d_codes.data_ptr(), d_flags=d_flags.data_ptr(),
+            d_n_aln=d_n.data_ptr(), d_res=d_res.data_ptr(), d_counters=d_ctr.data_ptr(), max_len=int(lens.max())))
+        torch.cuda.synchronize()
+        dev = d_res.cpu().numpy().view(np.uint32).reshape(n, SP_RES_WORDS)
+        assert int(d_ctr[0]) == n
+        assert np.array_equal(host[:, :2], dev[:, :2]), "status / n_aln differ between the entry points"
+        spliced.append(0)
+        for k in range(n):
+            if host[k, 0] == 0:                     # answered: 9 words per hit, nothing written past them
+                w = 2 + 9 * int(host[k, 1])
+                assert np.array_equal(host[k, 2:w], dev[k, 2:w]), f"read {k} of {n}: hits differ"
+                spliced[-1] += int(host[k, 1] > 0)
+    gi.close()
+    assert spliced[0] > 0
