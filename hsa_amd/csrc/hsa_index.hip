@@ -350,10 +350,69 @@ static int build_tries_t(hsa_index *ix, RD rev, IT T, const IT *C)
     return 0;
 }
 
+// The implicit root levels of hsa_trie.h: level after level of the prepend trie on the
+// forward BWT, each from the one before, until a level is not complete (some string of
+// that length does not occur), HSA_SDEPTH levels are built (default HSA_SDEPTH_DEFAULT, at
+// most HSA_SDEPTH_MAX; 0 = none) or the next level does not fit in device memory.  Only the
+// deepest complete level is kept.  Like the width trie it only saves rank steps: none
+// (sdepth 0) is not an error.
+static int build_search_levels(hsa_index *ix)
+{
+    uint32_t D = HSA_SDEPTH_DEFAULT;
+    if (const char *e = getenv("HSA_SDEPTH")) {
+        const int v = atoi(e);
+        D = v < 0 ? 0u : (uint32_t)v > HSA_SDEPTH_MAX ? HSA_SDEPTH_MAX : (uint32_t)v;
+    }
+    ix->sdepth = 0;
+    ix->d_trie_s = nullptr;
+    if (D == 0) return 0;
+    TrieC<uint32_t> Cv;
+    for (int c = 0; c < 4; ++c) Cv.v[c] = ix->C[c];
+    const RankDir fwd{ix->blk[0], ix->isa0};
+    unsigned *d_bad = nullptr;
+    HSA_HIP(hipMalloc(&d_bad, 4));
+    HSA_HIP(hipMemsetAsync(d_bad, 0, 4, ix->stream));
+    void *cur = nullptr;                         // level `depth`, complete (null: the root)
+    uint32_t depth = 0;
+    int rc = 0;
+    // a level of 4^d strings is complete only in a text of at least 4^d characters
+    while (depth < D && (1ull << (2 * (depth + 1))) <= (uint64_t)ix->T) {
+        void *nxt = nullptr;
+        if (hipMalloc(&nxt, (size_t)64 << (2 * depth)) != hipSuccess) {
+            (void)hipGetLastError();
+            if (getenv("HSA_VERBOSE")) fprintf(stderr, "[hsa] implicit levels: no device memory past level %u\n", depth);
+            break;
+        }
+        unsigned bad = 0;
+        const unsigned nb = (unsigned)(((1ull << (2 * depth)) + 255) / 256);
+        hipLaunchKernelGGL(k_trie_search_level, dim3(nb), dim3(256), 0, ix->stream, fwd, ix->T, Cv, depth, cur, nxt, d_bad);
+        if (hipGetLastError() != hipSuccess ||
+            hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, ix->stream) != hipSuccess ||
+            hipStreamSynchronize(ix->stream) != hipSuccess) {
+            hsa_set_error("implicit levels: building level %u failed", depth + 1);
+            (void)hipFree(nxt);
+            rc = HSA_E_HIP;
+            break;
+        }
+        if (bad) { (void)hipFree(nxt); break; }  // level depth + 1 is not complete
+        (void)hipFree(cur);
+        cur = nxt;
+        ++depth;
+    }
+    (void)hipFree(d_bad);
+    if (rc) { (void)hipFree(cur); return rc; }
+    ix->d_trie_s = cur;
+    ix->sdepth = depth;
+    if (getenv("HSA_VERBOSE")) fprintf(stderr, "[hsa] implicit levels: %u (%zu bytes)\n", depth, depth ? (size_t)16 << (2 * depth) : (size_t)0);
+    return 0;
+}
+
 static int build_tries(hsa_index *ix)
 {
+    // (a wide index has no implicit levels: the 64-bit kernels do not carry them)
     if (ix->wide) return build_tries_t<uint64_t, RankDir64>(ix, hsa_rank_dir64(ix, 1), ix->T64, ix->C64);
-    return build_tries_t<uint32_t, RankDir>(ix, RankDir{ix->blk[1], ix->risa0}, ix->T, ix->C);
+    if (int rc = build_tries_t<uint32_t, RankDir>(ix, RankDir{ix->blk[1], ix->risa0}, ix->T, ix->C)) return rc;
+    return build_search_levels(ix);
 }
 
 int hsa_need32(const hsa_index *ix)
@@ -484,6 +543,7 @@ extern "C" int hsa_index_clone(hsa_index_t *src, hsa_index_t **out)
     ix->d_trie_w = root->d_trie_w;
     ix->trie_depth = root->trie_depth;
     ix->trie_wide = root->trie_wide; ix->trie_bytes = root->trie_bytes;
+    ix->d_trie_s = root->d_trie_s; ix->sdepth = root->sdepth;
     ix->parent = root;
     __atomic_add_fetch(&root->n_clones, 1, __ATOMIC_ACQ_REL);
     *out = ix;
@@ -522,6 +582,7 @@ extern "C" void hsa_index_free(hsa_index_t *ix)
         ix->d_sa = ix->d_blocks = nullptr;
         ix->d_text = nullptr;
         ix->d_trie_w = nullptr;
+        ix->d_trie_s = nullptr;
     }
     (void)hipFree(ix->blk_base[0]); (void)hipFree(ix->blk_base[1]);
     hsa_scratch_free(ix->main); hsa_scratch_free(ix->big); hsa_scratch_free(ix->huge);
@@ -538,6 +599,7 @@ extern "C" void hsa_index_free(hsa_index_t *ix)
     (void)hipFree(ix->d_sa); (void)hipFree(ix->d_blocks); (void)hipFree(ix->d_text);
     if (ix->d_sp) (void)hipFree(ix->d_sp);
     (void)hipFree(ix->d_trie_w);
+    (void)hipFree(ix->d_trie_s);
     if (ix->ev0) (void)hipEventDestroy(ix->ev0);
     if (ix->ev1) (void)hipEventDestroy(ix->ev1);
     if (ix->evm) (void)hipEventDestroy(ix->evm);
@@ -558,7 +620,7 @@ extern "C" int hsa_index_is64(const hsa_index_t *ix) { return ix->is64 ? 1 : 0; 
 extern "C" int hsa_index_trie(const hsa_index_t *ix, uint32_t *depth, uint32_t *sdepth, size_t *bytes)
 {
     if (depth) *depth = ix->trie_depth;
-    if (sdepth) *sdepth = 0;                   // no search trie (hsa_trie.h)
+    if (sdepth) *sdepth = ix->sdepth;          // k_search's implicit root levels (hsa_trie.h)
     if (bytes) *bytes = ix->trie_bytes;
     return 0;
 }

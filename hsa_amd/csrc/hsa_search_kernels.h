@@ -154,6 +154,12 @@ struct SearchArgs {
                                    // [3] lanes waiting [4] offers [5] offers refused (capacity) [6] sub-
                                    // searches ended [7] owners answered by their helpers [8] sub-searches'
                                    // rank queries [9] ready-queue tail
+    // the implicit root levels (hsa_trie.h; ungapped 32-bit kernels with 8/16-bit rows, not
+    // the HUGE pass): level sdc of the index's prepend trie, one 64-byte sector per
+    // level-(sdc - 1) node; sdc 0: none.  (Last in the struct: the gapped kernels' argument
+    // offsets stay what they were.)
+    const void *stw;
+    uint32_t sdc;
 };
 #define FR_HIT 0x80000000u
 #define FR_DONE 0x40000000u
@@ -794,6 +800,12 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
     // the 64-bit 4-bit-row kernels spilled with it)
     constexpr bool FRH = !HUGE && HSA_HELPERS && GAPS && sizeof(IT) == 4 && !WFmt<WT>::NIB;
     constexpr uint32_t NIL = HUGE ? 0xFFFFFFFFu : (uint32_t)NIL16;
+    // the implicit root levels (SearchArgs::sdc, hsa_trie.h).  Without indels an entry at
+    // read position i stands for a string of exactly len - i characters, and on a level of
+    // which every string occurs nothing reads its interval: a read longer than sdc keeps
+    // its entries of fewer than sdc characters as trie node numbers (Ent::x; y and z
+    // unused) and expands them without a rank step.  The root {0, T, 0} is node 0 as it is.
+    constexpr bool IMP = !GAPS && !HUGE && sizeof(IT) == 4 && !WFmt<WT>::NIB;
 #ifdef HSA_DIAG
     if (threadIdx.x == 0 && blockIdx.x < 8192) {
         g_diag[blockIdx.x * 4 + 0] = __builtin_amdgcn_s_memtime();
@@ -1472,6 +1484,28 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
             }
             const uint32_t ph = C_PH(ctl);
             if (ph == PH_EXACT) {
+                if constexpr (IMP) {
+                    // an exact tail inside the implicit levels (the string so far has
+                    // len - 1 - pos characters, ik is its node): the bases up to level sdc
+                    // are appended here, without a load (the reference issues the two
+                    // queries of each), and the level-sdc node's interval comes from the
+                    // table in (C); the rank steps go on from there.  len > sdc: pos stays > 0.
+                    const uint32_t len = (uint32_t)C_LEN(ctl);
+                    if (len > a.sdc && len - 1u - pos < a.sdc) {
+                        uint32_t c;
+                        for (;;) {
+                            c = getc((int)pos);
+                            if (c > 3) break;                                 // 2BWT-Interface.c:377
+                            ik = ik * 4u + c;
+                            st_q += 2u;
+                            if (len - pos == a.sdc) break;
+                            --pos;
+                        }
+                        if (c > 3) { SET_PH(ctl, PH_POP); continue; }
+                        req = 3; rp1 = ik;
+                        break;
+                    }
+                }
                 if constexpr (F::NIB) {
                     // the rank step goes out with the base load; an N (c > 3) drops it in (D)
                     cur_c = getc((int)pos);
@@ -1564,6 +1598,13 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
                 continue;
             }
             req = 1; rp1 = e.x; rp2 = e.y + 1u;
+            if constexpr (IMP) {
+                // an implicit entry (node e.x, fewer than sdc characters): its children are
+                // nodes too and need no load (req 4), or, on level sdc, come with their
+                // intervals from the node's table sector (req 2)
+                const uint32_t len = (uint32_t)C_LEN(ctl), dp = len - (uint32_t)ei;
+                if (len > a.sdc && dp < a.sdc) req = dp + 1u == a.sdc ? 2 : 4;
+            }
             if constexpr (F::NIB) cur_c = getc(ei - 1);                  // the expansion's base (D)
             SET_PH(ctl, PH_EXPAND);
         } while (0);
@@ -1572,20 +1613,29 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
         TMARK(1);
 #endif
         // ---------------- (C) the rank step
-        IT oa[4], ob[4];
+        IT oa[4], ob[4], srk[4];
 #ifdef HSA_DIAG
         {
-            const uint64_t rq = __ballot(req);
+            const uint64_t rq = __ballot(req == 1);
             if (lane == 0) dc[6] += (uint32_t)__popcll(rq);
             const uint32_t ph0 = C_PH(ctl);
-            if (req) DC(ph0 == PH_EXACT ? 1 : 2);
-            if (req && rp2 == rp1 + 1u) DC(ph0 == PH_EXACT ? 16 : 17);
+            if (req == 1) DC(ph0 == PH_EXACT ? 1 : 2);
+            if (req == 1 && rp2 == rp1 + 1u) DC(ph0 == PH_EXACT ? 16 : 17);
         }
 #endif
         uint32_t two = 0;
 #ifdef HSA_DIAG
         rd_steps += req == 1 ? 1u : 0u;
 #endif
+        if constexpr (IMP) {
+            // the implicit levels' table loads, issued ahead of the other lanes' rank loads
+            // so that the wave waits for both at once
+            if (req == 2) {
+                trie_s_load4(a.stw, rp1, oa, ob, srk);
+            } else if (req == 3) {
+                trie_s_load1(a.stw, rp1, oa[0], ob[0], srk[0]);
+            }
+        }
         if (req == 1) {
             two = occ_pair(Ix<IT>::fwd(a), rp1, rp2, oa, ob) - 1u;
             st_q += 2u; st_b += 1u + two;
@@ -1597,7 +1647,16 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
 #endif
         // ---------------- (D) apply
         const uint32_t ph = C_PH(ctl);
-        if (F::NIB && req == 1 && ph == PH_EXACT && cur_c > 3) {
+        if (IMP && req == 3) {
+            // the exact tail leaves the implicit levels: the level-sdc node's interval.  The
+            // write-back guard below tests which fields of the entry the tail started from
+            // are zero.  Of a string on a complete level none is (the builder checks
+            // k >= 1 and rev_k >= 1, and l >= k, rev_l >= rev_k), so a node entry gets
+            // non-zero fields here; the root keeps its own, {0, T, 0}.
+            ik = oa[0]; il = ob[0]; aux = srk[0] + (il - ik);
+            if (M_I(e.w) != C_LEN(ctl)) e.x = e.y = e.z = 1u;
+            --pos;
+        } else if (F::NIB && req == 1 && ph == PH_EXACT && cur_c > 3) {
             st_q -= 2u; st_b -= 1u + two;                                // not a step (2BWT-Interface.c:377)
             SET_PH(ctl, PH_POP);
         } else if (req && ph == PH_EXACT) {
@@ -1628,9 +1687,18 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
             const int est = M_ST(m), emm = M_MM(m), ego = M_GO(m), ege = M_GE(m);
             const int em = m_of(m);
             const int len = C_LEN(ctl);
-            IT srk[4];
             uint32_t ne = 0;                                             // children that occur
-            {
+            if (IMP && req != 1) {
+                // implicit levels: all four children occur; they are the nodes 4 p + c, or
+                // (req 2) the table's level-sdc intervals, already in oa, ob, srk.  The
+                // reference issues the step's two queries.
+                if (req == 4) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) { oa[c] = ek * 4u + (IT)c; ob[c] = 0; srk[c] = 0; }
+                }
+                ne = 0xFu;
+                st_q += 2u;
+            } else {
                 IT oc = 0;
 #pragma unroll
                 for (int c = 3; c >= 0; --c) {
@@ -1640,9 +1708,9 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
                     srk[c] = (erl - oc) - (ob[c] - oa[c]);
                     oc += d;
                 }
-            }
 #pragma unroll
-            for (int c = 0; c < 4; ++c) ne |= (oa[c] <= ob[c] ? 1u : 0u) << c;
+                for (int c = 0; c < 4; ++c) ne |= (oa[c] <= ob[c] ? 1u : 0u) << c;
+            }
             int allow_diff = 1, allow_M = 1;
             if (i > 0) {
                 // width[i-1].bid, width[i].bid and w[i-1] == w[i] (bwtgap.c:256-258)

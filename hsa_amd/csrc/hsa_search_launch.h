@@ -371,6 +371,8 @@ static int pass_args(hsa_index *ix, const LaunchPlan &P, SearchScratch &S, const
     A.split = 0; A.sp_n = nullptr; A.sp_off = nullptr; A.sp_q = nullptr; A.sp_p = nullptr;
     A.ktd = trie_levels(ix, sizeof(IT) == 8);
     A.ktw = A.ktd ? ix->d_trie_w : nullptr;
+    A.sdc = sizeof(IT) == 4 ? ix->sdepth : 0u;
+    A.stw = A.sdc ? ix->d_trie_s : nullptr;
     A.wkey = nullptr; A.perm = nullptr; A.okey = 0;
     A.fwd_list = nullptr; A.fwd_n = nullptr; A.fwd_only = 0; A.rmap = nullptr;
     A.fr_budget = 0; A.fr_demand = 0; A.fr_cap = 0;

@@ -22,9 +22,21 @@
 // The width trie (k_widths): c APPENDED (forward extension on the reverse BWT,
 // BWTSARangeForeward, 2BWT-Interface.c:121-131): entry {k, l}; node p's children at
 // 4 p + c on the next level.  Level d (1..D) holds 4^d entries from entry (4^d - 4) / 3.
-// (A search trie for k_search -- c prepended, with exact-tail jumps -- was built and
-// measured slower than the rank steps it replaced, at every depth, in large and in
-// 100 000-read batches: DESIGN.md.)
+//
+// The implicit root levels (k_search, ungapped): c PREPENDED (the bidirectional backward
+// step on the forward BWT, 2BWT-Interface.c:235-272); node p's children at 4 p + c.  A
+// search trie that answered each shallow step with a table load was built and measured
+// slower than the rank steps it replaced ("Measured and removed"): the wave
+// still waited for one load per step.  Here the shallow steps take NO load.  On a level
+// of which every string occurs in the text (a COMPLETE level: all of a node's four
+// children exist) an ungapped search reads nothing of an entry's interval until it
+// leaves the level -- pruning works on the width rows and the entry's meta word -- so
+// k_search carries the node number instead and only level Dc is kept, Dc being the
+// deepest complete level (at most HSA_SDEPTH, HSA_SDEPTH_MAX): {k, l, rev_k} per node, the
+// four children of one level-(Dc - 1) node in one 64-byte sector, words [0,4) their k,
+// [4,8) their l, [8,12) their rev_k.  16 B x 4^Dc.  The levels are the kernel's own
+// step arithmetic applied to the previous level, so the values are bit-identical to
+// the rank steps'.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -83,4 +95,60 @@ __global__ void __launch_bounds__(256) k_trie_width_level(RD rev, IT T, TrieC<IT
             trie_w_store<IT>(tw, ch + c, kc, lc);
         }
     }
+}
+
+// ---------------------------------------------------------------- implicit root levels
+#define HSA_SDEPTH_MAX 13u          // 16 B x 4^13 = 1 GiB
+#define HSA_SDEPTH_DEFAULT 13u
+
+// the level-Dc sector of level-(Dc - 1) node p: its four children's k, l, rev_k
+__device__ __forceinline__ void trie_s_load4(const void *t, uint32_t p, uint32_t k[4], uint32_t l[4], uint32_t rk[4])
+{
+    const uint4 *s = reinterpret_cast<const uint4 *>(t) + (size_t)p * 4;
+    const uint4 vk = s[0], vl = s[1], vr = s[2];
+    k[0] = vk.x; k[1] = vk.y; k[2] = vk.z; k[3] = vk.w;
+    l[0] = vl.x; l[1] = vl.y; l[2] = vl.z; l[3] = vl.w;
+    rk[0] = vr.x; rk[1] = vr.y; rk[2] = vr.z; rk[3] = vr.w;
+}
+
+// one level-Dc node n (child n & 3 of node n >> 2)
+__device__ __forceinline__ void trie_s_load1(const void *t, uint32_t n, uint32_t &k, uint32_t &l, uint32_t &rk)
+{
+    const uint32_t *s = reinterpret_cast<const uint32_t *>(t) + (size_t)(n >> 2) * 16 + (n & 3u);
+    k = s[0]; l = s[4]; rk = s[8];
+}
+
+// Level d (src; the root when d == 0) -> level d + 1 (dst, 4^d sectors): k_search's
+// expansion arithmetic (2BWT-Interface.c:235-272) on the forward BWT.  *bad is raised
+// when level d + 1 is not complete: a child that does not occur, or one with a zero k or
+// rev_k (k_search's exact tail relies on both being non-zero below the root), or an
+// interval past the text.  The caller launches it only on a complete level d, so every
+// rank position is inside the text.
+static __global__ void __launch_bounds__(256) k_trie_search_level(RankDir fwd, uint32_t T, TrieC<uint32_t> Cg, uint32_t d,
+                                                                  const void *__restrict__ src, void *__restrict__ dst,
+                                                                  unsigned *bad)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= (1ull << (2u * d))) return;
+    uint32_t k = 0, l = T, rk = 0;
+    if (d > 0) trie_s_load1(src, (uint32_t)p, k, l, rk);
+    uint32_t oa[4], ob[4], sr[4];
+    occ_pair(fwd, k, l + 1u, oa, ob);
+    const uint32_t erl = rk + (l - k);
+    uint32_t oc = 0;
+    bool ok = true;
+    for (int c = 3; c >= 0; --c) {
+        const uint32_t n = ob[c] - oa[c];
+        oa[c] = Cg.v[c] + oa[c] + 1u;
+        ob[c] = Cg.v[c] + ob[c];
+        sr[c] = (erl - oc) - (ob[c] - oa[c]);
+        oc += n;
+        ok = ok && oa[c] >= 1u && oa[c] <= ob[c] && ob[c] <= T && sr[c] >= 1u;
+    }
+    uint4 *s = reinterpret_cast<uint4 *>(dst) + p * 4;
+    s[0] = make_uint4(oa[0], oa[1], oa[2], oa[3]);
+    s[1] = make_uint4(ob[0], ob[1], ob[2], ob[3]);
+    s[2] = make_uint4(sr[0], sr[1], sr[2], sr[3]);
+    s[3] = make_uint4(0u, 0u, 0u, 0u);
+    if (!ok) *bad = 1u;
 }

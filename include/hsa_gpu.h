@@ -99,8 +99,11 @@ size_t hsa_index_bytes(const hsa_index_t *ix);
 int  hsa_index_device(const hsa_index_t *ix);
 /* The index's root width trie (hsa_amd/csrc/hsa_trie.h): every string of up to *depth
  * characters with the interval k_widths' forward extension computes for it (0: none;
- * HSA_TRIE_DEPTH at creation, default 12); *sdepth is 0 (k_search takes rank steps
- * only); *bytes of device memory it takes.  Its loads are counted in d_counters[10]. */
+ * HSA_TRIE_DEPTH at creation, default 12); *bytes of device memory it takes.  Its loads
+ * are counted in d_counters[10].  *sdepth: the implicit root levels of the ungapped
+ * k_search -- the deepest level of which every string occurs in the text, at most
+ * HSA_SDEPTH at creation (default and most 13; 0: none, as for a 64-bit index); its
+ * table, 16 B x 4^sdepth, is not part of *bytes. */
 int  hsa_index_trie(const hsa_index_t *ix, uint32_t *depth, uint32_t *sdepth, size_t *bytes);
 /* A second handle on the same resident index, for passes that run concurrently: the
  * clone shares src's read-only device arrays (rank blocks, wrap tables, trie, SA) and
