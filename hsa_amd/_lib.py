@@ -34,7 +34,8 @@ EXPORTS = [  # every symbol include/hsa_gpu.h and include/hsa_bwtaln.h declare
     "hsa_build_bwt_index_device", "hsa_extend_batch", "bwt_extend_foreward", "bwt_extend_backward",
     "hsa_width0_batch", "bwt_cal_width", "hsa_extend_sliced", "hsa_index_trie",
     "hsa_index_clone", "hsa_splice_prefetch_batch", "hsa_index_set_text", "hsa_splice_match_batch",
-    "hsa_splice_device",
+    "hsa_splice_device", "hsa_build_bwt_index_device64", "hsa_index_set_sa64", "hsa_index_set_sa64_device",
+    "hsa_sa_position_batch64", "hsa_sa_position_device64", "hsa_psi_minus_batch64", "hsa_hit_positions_device64",
 ]
 SP_RES_WORDS = 20  # hsa_splice_match_batch's per-read answer (include/hsa_gpu.h)
 ALN64_WORDS = 14   # hsa_aln64_t (include/hsa_gpu.h)
@@ -123,6 +124,14 @@ class DeviceBatch(C.Structure):
                 ("d_flags", C.c_void_p), ("d_hit_off", C.c_void_p), ("d_hits", C.c_void_p),
                 ("hit_cap", C.c_uint64), ("d_counters", C.c_void_p), ("max_len", C.c_int32),
                 ("max_seed", C.c_int32)]
+
+
+class HitPosBatch64(C.Structure):
+    """hsa_hitpos_batch64_t (include/hsa_gpu.h): the hit lists of hsa_search_device64 to
+    positions, all device pointers."""
+    _fields_ = [("d_n_aln", C.c_void_p), ("d_hit_off", C.c_void_p), ("d_hits", C.c_void_p), ("n_jobs", C.c_int),
+                ("max_occ", C.c_uint32), ("d_pos_off", C.c_void_p), ("d_pos", C.c_void_p), ("d_pos_hit", C.c_void_p),
+                ("pos_cap", C.c_uint64), ("d_counters", C.c_void_p)]
 
 
 class SeedBatch(C.Structure):
@@ -252,6 +261,15 @@ def lib():
     if hasattr(L, "hsa_build_bwt_index_device"):
         L.hsa_build_bwt_index_device.argtypes = [C.c_int, C.c_uint64, vp, vp, C.POINTER(C.c_uint64), u64, C.c_uint32,
                                                  vp]
+    if hasattr(L, "hsa_index_set_sa64"):            # (older A/B builds lack the 64-bit positions)
+        L.hsa_build_bwt_index_device64.argtypes = [C.c_int, C.c_uint64, vp, vp, C.POINTER(C.c_uint64), u64, C.c_uint32,
+                                                   vp]
+        L.hsa_index_set_sa64.argtypes = [vp, u64, C.c_uint64, C.c_uint32, u64, C.c_int]
+        L.hsa_index_set_sa64_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, u64, C.c_int]
+        L.hsa_sa_position_batch64.argtypes = [vp, C.c_size_t, u64, u64]
+        L.hsa_sa_position_device64.argtypes = [vp, C.c_size_t, vp, vp, vp]
+        L.hsa_psi_minus_batch64.argtypes = [vp, C.c_size_t, u64, u64]
+        L.hsa_hit_positions_device64.argtypes = [vp, C.POINTER(HitPosBatch64), vp]
     if hasattr(L, "hsa_extend_batch"):
         L.hsa_extend_batch.argtypes = [vp, C.POINTER(Regime), C.c_int, vp, C.c_int, u8, i32, C.c_size_t, i32, i32,
                                        u32]
@@ -291,6 +309,65 @@ def probe_gather(table_bytes: int, per_sector: int = 1, device: int = 0) -> floa
 
 def configure(waves_per_cu=0, pool_entries=0, hit_cap=0):
     check(lib().hsa_configure(waves_per_cu, pool_entries, hit_cap))
+
+
+class DeviceU64:
+    """A hipMalloc'd array of u64 on the current device: the sample array of
+    build_bwt_index64, in the form hsa_index_set_sa64_device takes over (a torch tensor's
+    memory belongs to torch's allocator and cannot be handed to the library).  free()
+    unless an index took it (GpuIndex.set_sa64_device)."""
+
+    def __init__(self, n: int):
+        p = C.c_void_p()
+        rc = lib().hipMalloc(C.byref(p), C.c_size_t(8 * max(int(n), 1)))
+        if rc != 0 or not p.value:
+            raise HsaError(f"hipMalloc of {8 * n} bytes failed ({rc})")
+        self.ptr, self.n = p.value, int(n)
+
+    def write(self, first: int, values):
+        v = np.ascontiguousarray(values, np.uint64)
+        assert 0 <= first and first + len(v) <= self.n
+        rc = lib().hipMemcpy(C.c_void_p(self.ptr + 8 * first), v.ctypes.data_as(C.c_void_p), C.c_size_t(v.nbytes), 1)
+        if rc != 0:
+            raise HsaError(f"hipMemcpy to the device failed ({rc})")
+
+    def to_host(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        count = self.n - first if count is None else count
+        assert 0 <= first and first + count <= self.n
+        out = np.zeros(count, np.uint64)
+        rc = lib().hipMemcpy(out.ctypes.data_as(C.c_void_p), C.c_void_p(self.ptr + 8 * first), C.c_size_t(out.nbytes), 2)
+        if rc != 0:
+            raise HsaError(f"hipMemcpy from the device failed ({rc})")
+        return out
+
+    def free(self):
+        if self.ptr:
+            lib().hipFree(C.c_void_p(self.ptr))
+            self.ptr = None
+
+
+def build_bwt_index64(T: int, d_text: int, interval: int, device: int = 0):
+    """hsa_build_bwt_index_device64 of the text at device pointer d_text (LSB-first
+    2-bit codes, zero-padded): (the BWT codes as a torch int32 tensor on the device,
+    isa0, C[5] as u64, the samples as a DeviceU64 with entry 0 set to T).  The samples
+    stay on the device: GpuIndex.set_sa64_device takes them."""
+    import torch
+    nw = (T + 15) // 16
+    bw = torch.zeros(nw + 8, dtype=torch.int32, device=f"cuda:{device}")
+    torch.cuda.synchronize()
+    isa0 = C.c_uint64()
+    Cc = np.zeros(5, np.uint64)
+    sa = DeviceU64((T + interval) // interval) if interval else None
+    try:
+        check(lib().hsa_build_bwt_index_device64(device, T, d_text, bw.data_ptr(), C.byref(isa0), Cc, interval,
+                                                 sa.ptr if sa else None))
+        if sa:
+            sa.write(0, [T])
+    except Exception:
+        if sa:
+            sa.free()
+        raise
+    return bw, int(isa0.value), Cc, sa
 
 
 def _take_hits(hp, n):
@@ -463,6 +540,56 @@ class GpuIndex:
         out = np.zeros((len(idx), 4), np.uint32)
         check(lib().hsa_sa_position_batch(self.h, len(idx), idx, out))
         return out
+
+    @staticmethod
+    def _blocks64(blocks):
+        blk = np.ascontiguousarray(blocks, np.uint64).reshape(-1, 4)
+        return (blk.reshape(-1) if len(blk) else np.zeros(4, np.uint64)), len(blk)
+
+    def _handle(self):
+        if not getattr(self, "h", None):
+            raise HsaError("the index is closed (no handle)")
+        return self.h
+
+    def set_sa64(self, values, interval, blocks):
+        """hsa_index_set_sa64: the sampled SA as u64 values (values[r / interval] = SA[r],
+        values[0] = T) and the block table (rows of chrID, blockStart, blockEnd, ori as
+        u64), on an index of from_device_codes64."""
+        vals = np.ascontiguousarray(values, np.uint64)
+        blk, nb = self._blocks64(blocks)
+        check(lib().hsa_index_set_sa64(self._handle(), vals, len(vals), int(interval), blk, nb))
+
+    def set_sa64_device(self, ptr, n, interval, blocks):
+        """hsa_index_set_sa64_device: the same from a hipMalloc'd device array of n u64
+        (a DeviceU64 or its address), which the index owns from here on."""
+        blk, nb = self._blocks64(blocks)
+        p = ptr.ptr if isinstance(ptr, DeviceU64) else ptr
+        check(lib().hsa_index_set_sa64_device(self._handle(), p, int(n), int(interval), blk, nb))
+        if isinstance(ptr, DeviceU64):
+            ptr.ptr = None
+
+    def sa_positions64(self, idx):
+        """(SA value, chrID, 1-based position, text position) per SA index, u64; all-ones
+        where no block holds it, in all four for a walk cut by HSA_SA_MAX_WALK."""
+        idx = np.ascontiguousarray(idx, np.uint64)
+        out = np.zeros((len(idx), 4), np.uint64)
+        check(lib().hsa_sa_position_batch64(self._handle(), len(idx), idx, out))
+        return out
+
+    def psi_minus64(self, idx):
+        """One LF step per SA index (hsa_psi_minus_batch64); the '$' row answers 0."""
+        idx = np.ascontiguousarray(idx, np.uint64)
+        out = np.zeros(len(idx), np.uint64)
+        check(lib().hsa_psi_minus_batch64(self._handle(), len(idx), idx, out))
+        return out
+
+    def hit_positions64(self, batch: "HitPosBatch64", max_occ=None, stream=None):
+        """hsa_hit_positions_device64: the device hit lists of search_device64 to
+        positions (batch.d_pos_off, d_pos, d_pos_hit, d_counters) on `stream` (a
+        hipStream_t address; None: the index's own); does not synchronise."""
+        if max_occ is not None:
+            batch.max_occ = int(max_occ)
+        check(lib().hsa_hit_positions_device64(self._handle(), C.byref(batch), stream))
 
     def last_pass_ms(self):
         """(k_widths ms, k_search ms) of the last device pass on this index."""

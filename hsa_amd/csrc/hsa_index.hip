@@ -121,9 +121,10 @@ extern "C" int hsa_index_release_scratch(hsa_index_t *ix)
     (void)hipSetDevice(ix->device);
     HSA_HIP(hipStreamSynchronize(ix->stream));
     hsa_scratch_free(ix->main); hsa_scratch_free(ix->big); hsa_scratch_free(ix->huge);
-    void **bufs[] = {&ix->d_pf, &ix->d_pf2, &ix->d_sp, &ix->d_any, &ix->d_any_aux, &ix->d_help};
-    size_t *caps[] = {&ix->d_pf_cap, &ix->d_pf2_cap, &ix->d_sp_cap, &ix->d_any_cap, &ix->d_any_aux_cap, &ix->d_help_cap};
-    for (int i = 0; i < 6; ++i) {
+    void **bufs[] = {&ix->d_pf, &ix->d_pf2, &ix->d_sp, &ix->d_any, &ix->d_any_aux, &ix->d_help, &ix->d_hp};
+    size_t *caps[] = {&ix->d_pf_cap, &ix->d_pf2_cap, &ix->d_sp_cap, &ix->d_any_cap, &ix->d_any_aux_cap, &ix->d_help_cap,
+                      &ix->d_hp_cap};
+    for (int i = 0; i < 7; ++i) {
         if (*bufs[i]) (void)hipFree(*bufs[i]);
         *bufs[i] = nullptr;
         *caps[i] = 0;
@@ -540,6 +541,8 @@ extern "C" int hsa_index_clone(hsa_index_t *src, hsa_index_t **out)
     ix->d_sa = root->d_sa; ix->d_blocks = root->d_blocks;
     ix->d_text = root->d_text; ix->text_words = root->text_words; ix->dna_len = root->dna_len;
     ix->sa_interval = root->sa_interval; ix->n_blocks = root->n_blocks;
+    ix->d_sa64 = root->d_sa64; ix->d_blocks64 = root->d_blocks64;
+    ix->sa64_interval = root->sa64_interval; ix->n_blocks64 = root->n_blocks64;
     ix->d_trie_w = root->d_trie_w;
     ix->trie_depth = root->trie_depth;
     ix->trie_wide = root->trie_wide; ix->trie_bytes = root->trie_bytes;
@@ -580,6 +583,7 @@ extern "C" void hsa_index_free(hsa_index_t *ix)
             orphan = ix->parent;
         ix->blk_base[0] = ix->blk_base[1] = nullptr;
         ix->d_sa = ix->d_blocks = nullptr;
+        ix->d_sa64 = ix->d_blocks64 = nullptr;
         ix->d_text = nullptr;
         ix->d_trie_w = nullptr;
         ix->d_trie_s = nullptr;
@@ -597,6 +601,7 @@ extern "C" void hsa_index_free(hsa_index_t *ix)
     if (ix->h_pf) (void)hipHostFree(ix->h_pf);
     (void)hipFree(ix->d_in); (void)hipFree(ix->d_out); (void)hipFree(ix->d_ctr); (void)hipFree(ix->d_wrows); (void)hipFree(ix->d_ovf); (void)hipFree(ix->d_seed); (void)hipFree(ix->d_ext); (void)hipFree(ix->d_slices);
     (void)hipFree(ix->d_sa); (void)hipFree(ix->d_blocks); (void)hipFree(ix->d_text);
+    (void)hipFree(ix->d_sa64); (void)hipFree(ix->d_blocks64); (void)hipFree(ix->d_hp);
     if (ix->d_sp) (void)hipFree(ix->d_sp);
     (void)hipFree(ix->d_trie_w);
     (void)hipFree(ix->d_trie_s);

@@ -96,6 +96,11 @@ struct hsa_index {
     // sampled suffix array + chromosome blocks (SA -> position, hsa_sa.hip)
     uint32_t *d_sa = nullptr, *d_blocks = nullptr;
     uint32_t sa_interval = 0, n_blocks = 0;
+    // the same for a 64-bit index (hsa_index_set_sa64): u64 samples and four u64 per block;
+    // d_hp: hsa_hit_positions_device64's per-read row counts and scan scratch
+    uint64_t *d_sa64 = nullptr, *d_blocks64 = nullptr;
+    uint32_t sa64_interval = 0, n_blocks64 = 0;
+    void *d_hp = nullptr; size_t d_hp_cap = 0;
     // the packed text as the host's HSP holds it (hsa_index_set_text): 16 codes per u32,
     // the first in the high bits, text_words words as allocated (DNALoadPacked,
     // TextConverter.c:704-707), dna_len the HSP's dnaLength
@@ -146,6 +151,8 @@ int hsa_realloc_device(void **out, void **old, size_t bytes);
 // of a longer row (internal: the splice seeds, hsa_splice_prefetch.h): terminal computed, no export
 #define HSA_MG_PREFIX 0xFFFFFFFFFFFFFFFFull
 SaView hsa_sa_view(const hsa_index *ix);
+// The 64-bit view (hsa_index_set_sa64); max_walk: HSA_SA_MAX_WALK as read at the call
+SaView64 hsa_sa_view64(const hsa_index *ix, uint32_t max_walk);
 
 // The splice prefetch's device outputs (pf_dev, hsa_splice_prefetch.h), as the splice
 // path's kernel reads them (hsa_splice.hip).

@@ -23,6 +23,8 @@
  *                         (bwtgap.c:797-812) for every fallback read of a device batch.
  *   hsa_sa_position_*  -- BWTSaValue (BWT.c:1195) + BWTRetrievePositionFromSAIndex
  *                         (2BWT-Interface.c:329).
+ *   hsa_sa_position_*64, hsa_hit_positions_device64 -- the same on a 64-bit index (texts
+ *                         of 2^32 characters or more), which the reference cannot hold.
  *   hsa_extend_batch   -- bwt_extend_backward / bwt_extend_foreward (bwtgap.c:640-663,
  *                         bwt_backtracing_search :346-511): the splice path's seed
  *                         extensions.
@@ -475,6 +477,78 @@ int hsa_build_bwt_index_device(int device, uint64_t T, const uint32_t *d_text_ls
  * (u64 suffix positions past 2^32 characters). */
 int hsa_build_bwt_device64(int device, uint64_t T, const uint32_t *d_text_lsb, int reverse,
                            uint32_t *d_bwt_lsb, uint64_t *isa0, uint64_t C[5]);
+
+/* ---- text positions on the 64-bit path ----
+ * SA index -> text position for an index made by hsa_index_create_device64, of any
+ * length under 2^36 (no reference counterpart: the reference ends at 2^32 - 1
+ * characters).  Not built: a 64-bit splice path or SAM stage, and an on-disk format for
+ * 64-bit samples (the .sa file's values are u32).
+ *
+ * hsa_build_bwt_index_device64: hsa_build_bwt_index_device for any 1 <= T < 2^36, with
+ * u64 samples: d_sa64[r / sa_interval] = SA[r] for every row r > 0 with r % sa_interval
+ * == 0, over the T + 1 rows including '$'; entry 0 (the '$' row, SA = T) is the
+ * caller's.  d_sa64 holds (T + sa_interval) / sa_interval values, or is NULL (no
+ * samples); a non-null d_sa64 with sa_interval 0 is HSA_E_ARG. */
+int hsa_build_bwt_index_device64(int device, uint64_t T, const uint32_t *d_text_lsb,
+                                 uint32_t *d_bwt_lsb, uint64_t *isa0, uint64_t C[5],
+                                 uint32_t sa_interval, uint64_t *d_sa64);
+/* Attach the sampled suffix array (values[r / interval] = SA[r], values[0] = T; at least
+ * (T + interval) / interval values, HSA_E_ARG otherwise) and the chromosome block table
+ * (n_blocks rows of four u64: chrID, blockStart, blockEnd, ori).  Only on an index of
+ * hsa_index_create_device64 (HSA_E_ARG otherwise); under 2^32 characters
+ * hsa_index_set_sa keeps working beside it, with its own arrays.  Like hsa_index_set_sa
+ * they refuse a clone and an index with live clones; hsa_index_clone shares the arrays
+ * and hsa_index_free frees them.  The _device variant takes ownership of a device array
+ * (hipMalloc'd; the builder's output), so the samples of a 15 Gbp text (3.8 GB at
+ * interval 32) never cross PCIe; on an error the array stays the caller's. */
+int hsa_index_set_sa64(hsa_index_t *ix, const uint64_t *sa_values, uint64_t n_values,
+                       uint32_t interval, const uint64_t *blocks, int n_blocks);
+int hsa_index_set_sa64_device(hsa_index_t *ix, uint64_t *d_sa_values, uint64_t n_values,
+                              uint32_t interval, const uint64_t *blocks, int n_blocks);
+/* Output: 4 u64 per index -- SA value, chrID, 1-based position in the chromosome,
+ * position in the text; chrID and position are all-ones when no block holds it (the
+ * block search is hsa_sa_position_batch's on 64-bit fields).  An index is walked by LF
+ * steps (one 16-byte rank-block load each; the wrap table supplies the counts' high
+ * words) to the next sampled row, or to the row of the suffix at position 0 (isa0),
+ * where it ends: about `interval` steps, and values[0] is only returned for index 0.
+ * The walk is bounded: after HSA_SA_MAX_WALK steps (an environment variable read at
+ * each call; default 1 << 22) it stops and the index gets all-ones in all four words,
+ * as does an index > T.  On a sampled array that belongs to the index's BWT the bound
+ * never fires; it exists so that a mismatched pair ends instead of spinning on a shared
+ * device (the 32-bit walk, which follows the reference, has no bound).
+ * The _device variant launches on `stream` (NULL = the library's) and does not
+ * synchronise. */
+int hsa_sa_position_batch64 (hsa_index_t *ix, size_t n, const uint64_t *sa_index, uint64_t *out4);
+int hsa_sa_position_device64(hsa_index_t *ix, size_t n, const uint64_t *d_sa_index,
+                             uint64_t *d_out4, void *stream);
+/* One LF step per index (tests and tools, beside hsa_occ4_batch64): the row of the
+ * suffix one character longer; the '$' row (isa0) answers 0.  Indices 0..T (HSA_E_ARG
+ * past T).  Needs no suffix array. */
+int hsa_psi_minus_batch64   (hsa_index_t *ix, size_t n, const uint64_t *sa_index, uint64_t *out);
+
+/* The hit lists of hsa_search_device64, as they sit on the device, to positions.
+ * Read j's rows are its hit records in list order, each record's SA rows k .. l
+ * ascending, cut to the first max_occ (> 0) rows of the read as a whole; a read with
+ * n_aln <= 0 (no hit, or left with HSA_F_OVERFLOW) has none.  d_pos_off[j] is the first
+ * row of read j and d_pos_off[n_jobs] the total: in read order, so two runs give the
+ * same arrays (hit_off comes from the search's atomics and does not).  Row t: d_pos + 4 t
+ * as hsa_sa_position_device64 writes it, d_pos_hit[t] the index of its record within the
+ * read's list.  Rows past pos_cap are not written: d_counters[0] > d_counters[1] tells
+ * the caller to run again with more room (the hit_cap convention).  d_counters (>= 4
+ * u64, zeroed by the call): [0] rows wanted, [1] rows written, [2] walks cut by
+ * HSA_SA_MAX_WALK (those rows are all-ones).  d_hits must be 8-byte aligned.
+ * Three launches on `stream` (NULL = the library's), one lane per output row in the
+ * last; the call does not synchronise. */
+typedef struct {
+    const int32_t *d_n_aln; const uint64_t *d_hit_off; const uint32_t *d_hits; /* hsa_aln64_t */
+    int n_jobs; uint32_t max_occ;
+    uint64_t *d_pos_off;      /* n_jobs + 1: exclusive prefix sum of the per-read row counts */
+    uint64_t *d_pos;          /* 4 u64 per row, as hsa_sa_position_device64 */
+    uint32_t *d_pos_hit;      /* per row: index of its hit record within the read's list */
+    uint64_t pos_cap;         /* rows d_pos / d_pos_hit hold */
+    uint64_t *d_counters;     /* >= 4 u64: [0] rows wanted, [1] rows written, [2] walks cut by the bound */
+} hsa_hitpos_batch64_t;
+int hsa_hit_positions_device64(hsa_index_t *ix, const hsa_hitpos_batch64_t *b, void *stream);
 
 #ifdef __cplusplus
 }
