@@ -109,6 +109,53 @@ __device__ __forceinline__ uint32_t hsa_occ_pair(const RankDir d, uint32_t p1, u
     return 1u + ((p1 >> 6) != (p2 >> 6));
 }
 
+// One bidirectional step, all four characters: backward on the forward BWT
+// (BWTAllSARangesBackward_Bidirection, 2BWT-Interface.c:235-272), or forward on the
+// reverse BWT with the forward C table (BWTAllSARangesForward_Bidirection, :274).
+// d is the BWT stepped on; the caller has checked its positions against the text.
+__device__ __forceinline__ void hsa_step_all(const RankDir d, const uint32_t *C, int backward, uint32_t k, uint32_t l,
+                                             uint32_t rk, uint32_t rl, uint32_t ok[4], uint32_t ol[4], uint32_t ork[4],
+                                             uint32_t orl[4])
+{
+    uint32_t oL[4], oR[4], oC[4];
+    hsa_occ_pair(d, backward ? k : rk, (backward ? l : rl) + 1u, oL, oR);
+    oC[3] = 0;
+    for (int c = 2; c >= 0; --c) oC[c] = oC[c + 1] + oR[c + 1] - oL[c + 1];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        if (backward) {
+            ok[c] = C[c] + oL[c] + 1u;
+            ol[c] = C[c] + oR[c];
+            orl[c] = rl - oC[c];
+            ork[c] = orl[c] - (ol[c] - ok[c]);
+        } else {
+            ork[c] = C[c] + oL[c] + 1u;
+            orl[c] = C[c] + oR[c];
+            ol[c] = l - oC[c];
+            ok[c] = ol[c] - (orl[c] - ork[c]);
+        }
+    }
+}
+
+// gap_opt_t's mode bits and the states of a gapped search's entries (bwtaln.h, bwtgap.h)
+#define MODE_GAPE 0x01
+#define MODE_LOGGAP 0x04
+#define MODE_NONSTOP 0x10
+#define ST_M 0
+#define ST_I 1
+#define ST_D 2
+
+__device__ __forceinline__ int hsa_log2(uint32_t v)   // bwtgap.c:107-116
+{
+    int c = 0;
+    if (v & 0xffff0000u) { v >>= 16; c |= 16; }
+    if (v & 0xff00) { v >>= 8; c |= 8; }
+    if (v & 0xf0) { v >>= 4; c |= 4; }
+    if (v & 0xc) { v >>= 2; c |= 2; }
+    if (v & 0x2) c |= 1;
+    return c;
+}
+
 __device__ __forceinline__ void hsa_occ4(const RankDir d, uint32_t p, uint32_t o[4])
 {
     p -= (p > d.isa0);

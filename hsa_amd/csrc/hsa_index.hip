@@ -695,18 +695,10 @@ __global__ void k_step(RankDir d, const uint32_t *C, const uint32_t *in, size_t 
 {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint32_t k = in[4 * i], l = in[4 * i + 1], rl = in[4 * i + 3];
-    uint32_t a[4], b[4];
-    hsa_occ_pair(d, k, l + 1, a, b);
-    uint32_t oc[4];
-    oc[3] = 0;
-    for (int c = 2; c >= 0; --c) oc[c] = oc[c + 1] + b[c + 1] - a[c + 1];
+    uint32_t ok[4], ol[4], ork[4], orl[4];
+    hsa_step_all(d, C, 1, in[4 * i], in[4 * i + 1], in[4 * i + 2], in[4 * i + 3], ok, ol, ork, orl);
     uint32_t *o = out + 16 * i;
-    for (int c = 0; c < 4; ++c) {
-        uint32_t nk = C[c] + a[c] + 1, nl = C[c] + b[c];
-        uint32_t nrl = rl - oc[c];
-        o[c] = nk; o[4 + c] = nl; o[12 + c] = nrl; o[8 + c] = nrl - (nl - nk);
-    }
+    for (int c = 0; c < 4; ++c) { o[c] = ok[c]; o[4 + c] = ol[c]; o[8 + c] = ork[c]; o[12 + c] = orl[c]; }
 }
 
 extern "C" int hsa_step_batch(hsa_index_t *ix, size_t n, const uint32_t *klrr, uint32_t *out16)

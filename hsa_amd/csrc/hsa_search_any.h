@@ -354,7 +354,7 @@ __global__ void __launch_bounds__(64) k_search_any(AnyArgs a)
                         else if (s_b[ii - 1] == m_seed - 1 && s_b[ii] == m_seed - 1 && s_w[ii - 1] == s_w[ii]) allow_M = false;
                     }
                 }
-                const int tmp = (mode & MODE_LOGGAP) ? int_log2((uint32_t)(e.ge + e.go)) / 2 + 1 : e.go + e.ge;
+                const int tmp = (mode & MODE_LOGGAP) ? hsa_log2((uint32_t)(e.ge + e.go)) / 2 + 1 : e.go + e.ge;
                 if (allow_diff && i >= R.indel_end_skip + tmp && len - i >= R.indel_end_skip + tmp) {
                     if (e.st == ST_M) {
                         if (e.go < R.max_gapo) {

@@ -46,12 +46,6 @@
 #include "hsa_internal.h"
 #include "hsa_trie.h"
 
-#define MODE_GAPE 0x01
-#define MODE_LOGGAP 0x04
-#define MODE_NONSTOP 0x10
-#define ST_M 0
-#define ST_I 1
-#define ST_D 2
 #define NIL16 0xFFFFu
 #define BLOCK 256
 #define MAXB 128          // dense buckets per regime (BMask<2>)
@@ -299,17 +293,6 @@ __device__ __forceinline__ void ent_store(uint4 *pool, size_t base, uint32_t slo
 // for 32-bit intervals; hsa_aln64_t (include/hsa_gpu.h) for 64-bit ones
 template <typename IT> struct HitW { static constexpr uint32_t STAGE = sizeof(IT) == 4 ? 9u : 10u;
                                      static constexpr uint32_t OUT = sizeof(IT) == 4 ? 9u : 14u; };
-
-__device__ __forceinline__ int int_log2(uint32_t v)   // bwtgap.c:107-116
-{
-    int c = 0;
-    if (v & 0xffff0000u) { v >>= 16; c |= 16; }
-    if (v & 0xff00) { v >>= 8; c |= 8; }
-    if (v & 0xf0) { v >>= 4; c |= 4; }
-    if (v & 0xc) { v >>= 2; c |= 2; }
-    if (v & 0x2) c |= 1;
-    return c;
-}
 
 template <int MW> struct BMask;
 template <> struct BMask<0> {        // <= 32 buckets: one 32-bit word
@@ -1739,7 +1722,7 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
             uint32_t cand = 0;
             if constexpr (GAPS) {
                 const int ies = RG(indel_end_skip);
-                const int tmp = (R_MODE & MODE_LOGGAP) ? int_log2((uint32_t)(ege + ego)) / 2 + 1 : ego + ege;
+                const int tmp = (R_MODE & MODE_LOGGAP) ? hsa_log2((uint32_t)(ege + ego)) / 2 + 1 : ego + ege;
                 const bool ok = (allow_diff != 0) & ((R_MAXGO > 0) | (ego > 0)) & (i >= ies + tmp) & (len - i >= ies + tmp);
                 const IT occ = el - ek + 1u;
                 const uint32_t c_m = ego < R_MAXGO ? (1u | ne << 1) : 0u;

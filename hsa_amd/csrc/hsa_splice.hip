@@ -14,9 +14,11 @@
 //   done;
 // * the extension (bwt_extend_backward / _foreward -> bwt_backtracing_search,
 //   bwtgap.c:346-663) runs in the kernel's main loop, at ONE place for every lane of the
-//   wave, a few pops per lane per iteration -- the same search as k_extend
-//   (hsa_extend.hip): a bucketed LIFO per lane (heads and counts in LDS, 32-byte
-//   entries in an HBM pool with a free list), the entry pushed last kept in registers;
+//   wave, a few pops per lane per iteration.  The search is hsa_ext_search.h's, the one
+//   k_extend (hsa_extend.hip) runs; this kernel supplies its context (SpExt: the
+//   strand's read and width rows, the dense score -> bucket map, the hit rewritten in
+//   place) and the stack's bookkeeping (one packed head | count word per bucket in LDS,
+//   entries in the lane's HBM pool);
 // * bwt_aln_corelate_check (:669-742) and check_site_by_intron_end (:602-635) take their
 //   SA -> position lookups on the device (hsa_sa.h); splice_site_search_from_pos
 //   (:523-594) reads the packed reference the host's HSP holds (hsa_index_set_text).
@@ -36,6 +38,7 @@
 #include <string.h>
 
 #include "hsa_device.h"
+#include "hsa_ext_search.h"
 #include "hsa_internal.h"
 #include "hsa_sa.h"
 
@@ -45,12 +48,6 @@
 #define HSA_SP_BUDGET 16         // extension pops per lane per pass of the main loop
 #endif
 #define SP_POS_MAX 100           // bwt_aln_corelate_check: <= 10 hits x 10 positions (bwtgap.c:684-706)
-#define MODE_GAPE 0x01
-#define MODE_LOGGAP 0x04
-#define MODE_NONSTOP 0x10
-#define ST_M 0
-#define ST_I 1
-#define ST_D 2
 
 // resume points of sp_ctrl
 enum {
@@ -607,16 +604,38 @@ __device__ __noinline__ int sp_ctrl(const SpArgs &a, SpLane &S, uint32_t *lb)
     }
 }
 
-__device__ __forceinline__ int sp_log2(uint32_t v)   // bwtgap.c:107-116
-{
-    int c = 0;
-    if (v & 0xffff0000u) { v >>= 16; c |= 16; }
-    if (v & 0xff00) { v >>= 8; c |= 8; }
-    if (v & 0xf0) { v >>= 4; c |= 4; }
-    if (v & 0xc) { v >>= 2; c |= 2; }
-    if (v & 0x2) c |= 1;
-    return c;
-}
+// What ext_step (hsa_ext_search.h) needs from a lane of k_splice: the strand's read and
+// the prefetch's width rows, the dense bucket map, the hit rewritten in place.
+struct SpExt {
+    const SpArgs &a;
+    const hsa_regime_t &R;
+    const uint8_t *bmap;         // score -> bucket (LDS copy of a.bmap)
+    ExtStack<ExtBuckets16> stk;
+    ExtCall call;
+    int L;
+    uint32_t *aln;               // the hit being extended: A.a0 (foreward) or C.a0 (backward), in place
+    const uint8_t *seq;
+    const int32_t *w, *w6;       // width rows (bid in column 2p + 1); the anchor's six-column widths for p <= 12
+    __device__ __forceinline__ uint32_t seq_at(int p)
+    {
+        if (p < 0 || p >= L) { stk.err = EXT_E_WIN; return 4u; }
+        return seq[p];
+    }
+    __device__ __forceinline__ int bid_at(int p)
+    {
+        if (p < 0 || p > L) { stk.err = EXT_E_WIN; return 0; }
+        if (w6 && p <= 12) return w6[2 * p + 1];
+        return w[2 * p + 1];
+    }
+    __device__ __forceinline__ int bucket(int score) const
+    {
+        const uint32_t bk = bmap[score];
+        return bk == 0xffu ? -1 : (int)bk;
+    }
+    __device__ __forceinline__ uint32_t &hit(int w_) { return aln[w_]; }
+};
+static_assert(HSA_SP_CAP - EXT_E_CAP == 1 && HSA_SP_SCORE - EXT_E_SCORE == 1 && HSA_SP_RANK - EXT_E_RANK == 1 &&
+                  HSA_SP_WIN - EXT_E_WIN == 1, "k_splice reports an extension's EXT_E_* as HSA_SP_* = EXT_E_* + 1");
 
 #ifdef HSA_SP_DIAG
 __device__ unsigned long long g_spd[8];
@@ -630,237 +649,47 @@ __global__ void __launch_bounds__(SP_NT, 4) k_splice(SpArgs a)
     const uint32_t lane = blockIdx.x * SP_NT + threadIdx.x;
     SpLane &S = a.lanes[lane];
     uint32_t *const lb = a.lbuf + (size_t)lane * a.lbuf_words;
-    uint4 *const P = a.pool + (size_t)lane * a.cap * 2;
-    uint32_t *const hn = s_hn + threadIdx.x;
-    const int nst = (int)a.nb;                          // dense buckets
     const hsa_regime_t &R = a.rg;
 
-    // ---- the extension in flight (bwt_backtracing_search, bwtgap.c:346-511; k_extend)
-    bool x_on = false, x_pend = false;
-    int x_dir = 0, x_len = 0, x_start = 0, x_end = 0, x_mp0 = 0, x_mp = 0, x_best = 0, x_nent = 0, x_pscore = 0;
-    int x_err = 0, x_ret = 0, x_mode = 0, x_md = 0, x_L = 0, x_bscore = 0;
-    uint32_t x_top = 0, x_freel = SP_NIL;
-    uint4 x_pe0 = make_uint4(0, 0, 0, 0), x_pe1 = make_uint4(0, 0, 0, 0);
-    uint32_t *x_aln = nullptr;           // the hit being extended: A.a0 (foreward) or C.a0 (backward), in place
-    const uint8_t *x_seq = nullptr;
-    const int32_t *x_w = nullptr, *x_w6 = nullptr;
+    // ---- the extension in flight (hsa_ext_search.h): a bucketed LIFO per lane, packed
+    // heads and counts in LDS over the dense buckets, entries in the lane's HBM pool
+    SpExt X{a, R, s_bmap};
+    ExtStack<ExtBuckets16> &K = X.stk;
+    K.bk.hn = s_hn + threadIdx.x;
+    K.bk.hs = SP_NT;
+    K.P = a.pool + (size_t)lane * a.cap * 2;
+    K.cap = a.cap;
+    K.nb = (int)a.nb;
+    bool x_on = false;
+    int x_mp0 = 0;
     unsigned long long n_pops = 0, n_ext = 0, n_sa = 0;
-
-    auto seq_at = [&](int p) -> uint32_t {
-        if (p < 0 || p >= x_L) { x_err = HSA_SP_WIN; return 4u; }
-        return x_seq[p];
-    };
-    auto bid_at = [&](int p) -> int {
-        if (p < 0 || p > x_L) { x_err = HSA_SP_WIN; return 0; }
-        if (x_w6 && p <= 12) return x_w6[2 * p + 1];
-        return x_w[2 * p + 1];
-    };
-    auto flush = [&]() {                               // the pending entry into its bucket
-        x_pend = false;
-        uint32_t slot;
-        if (x_freel != SP_NIL) { slot = x_freel; x_freel = P[(size_t)slot * 2 + 1].z; }
-        else if (x_top < a.cap) slot = x_top++;
-        else { x_err = HSA_SP_CAP; return; }
-        const uint32_t v = hn[(uint32_t)x_pscore * SP_NT];
-        x_pe1.z = (v >> 16) ? (v & 0xFFFFu) : SP_NIL;
-        P[(size_t)slot * 2] = x_pe0;
-        P[(size_t)slot * 2 + 1] = x_pe1;
-        hn[(uint32_t)x_pscore * SP_NT] = slot | ((v >> 16) + 1u) << 16;
-        if (x_best > x_pscore) x_best = x_pscore;
-    };
-    auto push = [&](int i, uint32_t k, uint32_t l, uint32_t rk, uint32_t rl, int mm, int go, int ge, int st) {
-        const int score = mm * R.s_mm + go * R.s_gapo + ge * R.s_gape;      // gap_push (bwtgap.c:46-75)
-        if (score < 0 || score >= R.n_stacks) { x_err = HSA_SP_SCORE; return; }
-        const uint32_t bk = s_bmap[score];
-        if (bk == 0xffu) { x_err = HSA_SP_SCORE; return; }
-        if (x_pend) flush();
-        x_pe0 = make_uint4(k, l, rk, rl);
-        x_pe1 = make_uint4((uint32_t)score << 21 | (uint32_t)i,
-                           (uint32_t)(mm & 255) | (uint32_t)(go & 255) << 8 | (uint32_t)(ge & 255) << 16 |
-                               (uint32_t)(st & 3) << 24,
-                           0u, 0u);
-        x_pscore = (int)bk;                             // the bucket (score order)
-        x_pend = true;
-        ++x_nent;
-    };
-    auto step_all = [&](int backward, uint32_t k, uint32_t l, uint32_t rk, uint32_t rl, uint32_t ok[4], uint32_t ol[4],
-                        uint32_t ork[4], uint32_t orl[4]) {
-        uint32_t oL[4], oR[4], oC[4];
-        const uint32_t p1 = backward ? k : rk, p2 = (backward ? l : rl) + 1u, lim = (backward ? a.T : a.rT) + 1u;
-        if (p1 > lim || p2 > lim || p2 == 0u) { x_err = HSA_SP_RANK; return; }
-        hsa_occ_pair(backward ? a.fwd : a.rev, p1, p2, oL, oR);
-        oC[3] = 0;
-        for (int c = 2; c >= 0; --c) oC[c] = oC[c + 1] + oR[c + 1] - oL[c + 1];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            if (backward) {
-                ok[c] = a.C[c] + oL[c] + 1u;
-                ol[c] = a.C[c] + oR[c];
-                orl[c] = rl - oC[c];
-                ork[c] = orl[c] - (ol[c] - ok[c]);
-            } else {
-                ork[c] = a.C[c] + oL[c] + 1u;
-                orl[c] = a.C[c] + oR[c];
-                ol[c] = l - oC[c];
-                ok[c] = ol[c] - (orl[c] - ork[c]);
-            }
-        }
-    };
-    auto pk4 = [](const uint32_t v[4], uint32_t c) { return hsa_sel4<uint32_t>(c, v[0], v[1], v[2], v[3]); };
     // the extension S asks for (bwt_extend_foreward on A / bwt_extend_backward on C,
     // bwtgap.c:640-663): a fresh stack holding the hit
     auto ext_start = [&]() {
-        const int rr = S.read;
-        x_dir = S.xdir;
-        x_len = S.xl;
-        x_aln = x_dir ? S.C.a0 : S.A.a0;
-        x_start = (int)x_aln[6];
-        x_end = (int)x_aln[7];
-        x_mp0 = x_mp = S.max_pos;
-        x_mode = (R.mode & ~MODE_GAPE) | (S.gape ? MODE_GAPE : 0);
-        x_md = a.pf.amd[rr];
-        x_bscore = (x_md + 1) * R.s_mm + (R.max_gapo + 1) * R.s_gapo + (R.max_gape + 1) * R.s_gape;
-        x_L = S.L;
-        const int s = S.strand;
-        x_seq = a.pf.scodes + (size_t)(2 * rr + s) * a.pf.sc;
-        x_w = a.pf.rows + 2 * ((size_t)rr * 6u + (x_dir ? 0u : 4u) + (uint32_t)s) * a.pf.rs;   // width_back W1 / width_fore W0
-        x_w6 = (x_dir && S.anchor6) ? a.pf.cw + 2 * (8 * (size_t)rr + 6 + s) * a.pf.cws : nullptr;
-        for (int b = 0; b < nst; ++b) hn[(uint32_t)b * SP_NT] = 0;
-        x_best = nst; x_nent = 0; x_top = 0; x_freel = SP_NIL; x_pend = false; x_err = 0; x_ret = 0;
-        if (x_len < 0 && (x_mode & MODE_NONSTOP)) x_err = HSA_SP_WIN;    // a negative length read as 0xffff
-        else
-            push(x_len, x_aln[1], x_aln[2], x_aln[3], x_aln[4], (int)(x_aln[0] & 0xFFFFu), (int)((x_aln[0] >> 16) & 0xFFu),
-                 (int)(x_aln[0] >> 24), ST_M);                                        // bwtgap.c:644 / :658
+        const int rr = S.read, s = S.strand, dir = S.xdir;
+        X.aln = dir ? S.C.a0 : S.A.a0;
+        x_mp0 = S.max_pos;
+        X.call.set(dir, S.xl, (int)X.aln[6], (int)X.aln[7], x_mp0, a.pf.amd[rr],
+                   (R.mode & ~MODE_GAPE) | (S.gape ? MODE_GAPE : 0), R);
+        X.L = S.L;
+        X.seq = a.pf.scodes + (size_t)(2 * rr + s) * a.pf.sc;
+        X.w = a.pf.rows + 2 * ((size_t)rr * 6u + (dir ? 0u : 4u) + (uint32_t)s) * a.pf.rs;   // width_back W1 / width_fore W0
+        X.w6 = (dir && S.anchor6) ? a.pf.cw + 2 * (8 * (size_t)rr + 6 + s) * a.pf.cws : nullptr;
+        K.reset();
+        if (X.call.len < 0 && (X.call.mode & MODE_NONSTOP)) K.err = EXT_E_WIN;    // a negative length read as 0xffff
+        else ext_push_hit(X);
         x_on = true;
         ++n_ext;
     };
     auto ext_end = [&]() {
         x_on = false;
-        if (!x_err && x_ret != 1) x_ret = x_mp != x_mp0 ? 2 : -1;
+        if (!K.err && X.call.ret != 1) X.call.ret = X.call.max_pos != x_mp0 ? 2 : -1;
     };
-    // one gap_pop and its expansion (bwtgap.c:371-504)
+    // one gap_pop and its expansion (bwtgap.c:371-504), or the end of the search
     auto ext_pop = [&]() {
-        if (x_nent == 0 || x_err || x_nent > R.max_entries) { ext_end(); return; }
+        if (K.n_ent == 0 || K.err || K.n_ent > R.max_entries) { ext_end(); return; }
         ++n_pops;
-        uint4 e0, e1;
-        if (x_pend && x_pscore <= x_best) {
-            e0 = x_pe0; e1 = x_pe1;
-            x_pend = false;
-            --x_nent;
-        } else {
-            if (x_pend) { flush(); if (x_err) { ext_end(); return; } }
-            const uint32_t v = hn[(uint32_t)x_best * SP_NT];
-            const uint32_t slot = v & 0xFFFFu, nb = (v >> 16) - 1u;
-            e0 = P[(size_t)slot * 2]; e1 = P[(size_t)slot * 2 + 1];
-            hn[(uint32_t)x_best * SP_NT] = (e1.z & 0xFFFFu) | nb << 16;
-            --x_nent;
-            P[(size_t)slot * 2 + 1].z = x_freel;
-            x_freel = slot;
-            if (nb == 0 && x_nent > 0) {
-                int b = x_best + 1;
-                while (b < nst && (hn[(uint32_t)b * SP_NT] >> 16) == 0) ++b;
-                x_best = b;
-            } else if (nb == 0) {
-                x_best = nst;
-            }
-        }
-        uint32_t k = e0.x, l = e0.y, rk = e0.z, rl = e0.w;
-        const uint32_t info = e1.x;
-        const int e_mm = (int)(e1.y & 255u), e_go = (int)((e1.y >> 8) & 255u), e_ge = (int)((e1.y >> 16) & 255u);
-        const int e_st = (int)((e1.y >> 24) & 3u);
-        int i = (int)(info & 0xffffu);
-        if (!(x_mode & MODE_NONSTOP) && (int)(info >> 21) > x_bscore + R.s_mm) { ext_end(); return; }
-        int m = x_md - (e_mm + e_go);
-        if (x_mode & MODE_GAPE) m -= e_ge;
-        const int len = x_len, bw = x_dir, start = x_start, end = x_end;
-        if (m <= 0 || i == 0) {
-            if (m == 0 && i != 0) {
-                // bwt_extend_exact (2BWT-Interface.c:394-439)
-                uint32_t xk = k, xl = l, xrk = rk, xrl = rl;
-                if (bw == 1) {
-                    const int s0 = start - len - 1;
-                    while (i != 0 && !x_err) {
-                        const uint32_t c = seq_at(s0 + i);
-                        if (c > 3) break;
-                        uint32_t ok[4], ol[4], ork[4], orl[4];
-                        step_all(1, xk, xl, xrk, xrl, ok, ol, ork, orl);
-                        xk = pk4(ok, c); xl = pk4(ol, c); xrk = pk4(ork, c); xrl = pk4(orl, c);
-                        if (xk > xl) break;
-                        k = xk; l = xl; rk = xrk; rl = xrl;
-                        --i;
-                    }
-                } else {
-                    const int rp = end + len - i + 1;          // start + leav - leav: fixed (:424)
-                    while (!x_err) {
-                        const uint32_t c = seq_at(rp);
-                        if (c > 3) break;
-                        uint32_t ok[4], ol[4], ork[4], orl[4];
-                        step_all(0, xk, xl, xrk, xrl, ok, ol, ork, orl);
-                        xk = pk4(ok, c); xl = pk4(ol, c); xrk = pk4(ork, c); xrl = pk4(orl, c);
-                        if (xk > xl) break;
-                        k = xk; l = xl; rk = xrk; rl = xrl;
-                    }
-                }
-                if (x_err) { ext_end(); return; }
-            }
-            if (bw == 1 && x_mp >= start + i - len && (int)x_aln[6] > start + i - len) {
-                x_aln[6] = (uint32_t)(start + i - len);
-                x_mp = (int)x_aln[6];
-            } else if (bw == 0 && x_mp <= end + len - i && (int)x_aln[7] < end + len - i) {
-                x_aln[7] = (uint32_t)(end + len - i);
-                x_mp = (int)x_aln[7];
-            } else {
-                return;
-            }
-            x_aln[1] = k; x_aln[2] = l; x_aln[3] = rk; x_aln[4] = rl;
-            x_aln[5] = (x_aln[5] & 0xC0000000u) | 4u;                 // BWA_TYPE_SPLICING, strand kept
-            x_aln[0] = (uint32_t)e_mm | (uint32_t)e_go << 16 | (uint32_t)e_ge << 24;
-            x_aln[8] = info >> 21;
-            if (i == 0) { x_ret = 1; ext_end(); }
-            return;
-        }
-        --i;
-        const int real_pos = bw == 1 ? start - len + i : len + end - i;
-        uint32_t ok[4], ol[4], ork[4], orl[4];
-        step_all(bw, k, l, rk, rl, ok, ol, ork, orl);
-        if (x_err) { ext_end(); return; }
-        const uint32_t occ = l - k + 1u;
-        int allow_diff = 1;
-        if (bw == 1 && x_mp < real_pos) {
-            const int d = bid_at(real_pos) - bid_at(x_mp);
-            if (d > m || (d == m && bid_at(x_mp) != bid_at(x_mp + 1))) allow_diff = 0;
-        }
-        if (bw == 0 && x_mp > real_pos) {
-            const int d = bid_at(real_pos) - bid_at(x_mp);
-            if (d > m || (d == m && bid_at(x_mp) != bid_at(x_mp - 1))) allow_diff = 0;
-        }
-        const int tmp = (x_mode & MODE_LOGGAP) ? sp_log2((uint32_t)(e_ge + e_go)) / 2 + 1 : e_go + e_ge;
-        if (allow_diff && i >= R.indel_end_skip + tmp && len - i >= R.indel_end_skip + tmp) {
-            if (e_st == ST_M) {
-                if (e_go < R.max_gapo) {
-                    push(i, k, l, rk, rl, e_mm, e_go + 1, e_ge, ST_I);
-                    for (int j = 0; j != 4; ++j)
-                        if ((bw == 1 && ok[j] <= ol[j]) || (bw == 0 && ork[j] <= orl[j]))
-                            push(i + 1, ok[j], ol[j], ork[j], orl[j], e_mm, e_go + 1, e_ge, ST_D);
-                }
-            } else if (e_st == ST_I) {
-                if (e_ge < R.max_gape) push(i, k, l, rk, rl, e_mm, e_go, e_ge + 1, ST_I);
-            } else if (e_st == ST_D) {
-                if (e_ge < R.max_gape && (e_ge + e_go < x_md || occ < (uint32_t)R.max_del_occ))
-                    for (int j = 0; j != 4; ++j)
-                        if (ok[j] <= ol[j]) push(i + 1, ok[j], ol[j], ork[j], orl[j], e_mm, e_go, e_ge + 1, ST_D);
-            }
-        }
-        if (allow_diff == 1) {
-            const uint32_t sc = seq_at(real_pos);
-            for (int j = 1; j <= 4; ++j) {
-                const uint32_t c = (sc + (uint32_t)j) & 3u;
-                const int is_mm = (j != 4 || sc > 3) ? 1 : 0;
-                if ((bw == 1 && pk4(ok, c) <= pk4(ol, c)) || (bw == 0 && pk4(ork, c) <= pk4(orl, c)))
-                    push(i, pk4(ok, c), pk4(ol, c), pk4(ork, c), pk4(orl, c), e_mm + is_mm, e_go, e_ge, ST_M);
-            }
-        }
-        if (x_err) ext_end();
+        if (!ext_step(X)) ext_end();
     };
 
 #ifdef HSA_SP_DIAG
@@ -900,13 +729,13 @@ __global__ void __launch_bounds__(SP_NT, 4) k_splice(SpArgs a)
         if (x_on) {                                     // one place for every lane's extension
             for (int q = 0; q < HSA_SP_BUDGET && x_on; ++q) ext_pop();
             if (!x_on) {
-                if (x_err) {
-                    S.status = x_err;
+                if (K.err) {
+                    S.status = K.err + (HSA_SP_CAP - EXT_E_CAP);
                     sp_finish(a, S);
                     cur = -1;
                 } else {
-                    S.max_pos = x_mp;
-                    S.ext_ret = x_ret;
+                    S.max_pos = X.call.max_pos;
+                    S.ext_ret = X.call.ret;
                 }
             }
         }

@@ -12,7 +12,13 @@ from golden_io import EXTCAP_CASES, INDEX, load_extcap
 pytestmark = pytest.mark.gpu
 
 
-def ext_batch(name):
+HBM_STACKS = 200      # > EXT_LDS_NB (128): bucket heads and counts in HBM; <= HSA_EXT_SLICE_STACKS (256)
+
+
+def ext_batch(name, n_stacks=None):
+    """The recorded calls as one batch.  n_stacks replaces every regime's bucket count: a
+    larger one only adds buckets no entry reaches (best_score and every test of the
+    expansion are independent of it), so the results stay the reference's."""
     from hsa_amd._lib import EXT_DTYPE, Regime
     calls = list(load_extcap(name))
     keys, regimes = {}, []
@@ -26,7 +32,8 @@ def ext_batch(name):
             keys[key] = len(regimes)
             regimes.append(Regime(s_mm=o[0], s_gapo=o[1], s_gape=o[2], mode=o[3], indel_end_skip=o[4],
                                   max_del_occ=o[5], max_entries=o[6], max_gapo=o[9], max_gape=o[10],
-                                  max_seed_diff=o[11], max_top2=o[14], n_stacks=c["n_stacks"], max_diff=o[8]))
+                                  max_seed_diff=o[11], max_top2=o[14], n_stacks=n_stacks or c["n_stacks"],
+                                  max_diff=o[8]))
         jobs[j] = (c["dir"], c["len"], c["max_pos"], keys[key], c["lo"], len(c["seq"]), off, c["aln_in"], 0)
         codes.append(c["seq"])
         bids.append(c["bid"])
@@ -34,12 +41,11 @@ def ext_batch(name):
     return calls, regimes, jobs, np.concatenate(codes), np.concatenate(bids)
 
 
-@pytest.mark.parametrize("name", EXTCAP_CASES)
-def test_extension_batch_matches_reference(name):
+def check_batch(name, n_stacks=None):
     from hsa_amd import _lib, index_io
     fwd, rev = index_io.read_index(INDEX["tiny"])
     gi = _lib.GpuIndex(fwd, rev, device=0)
-    calls, regimes, jobs, codes, bids = ext_batch(name)
+    calls, regimes, jobs, codes, bids = ext_batch(name, n_stacks)
     ret, mp, aln = gi.extend(regimes, jobs, codes, bids)
     bad = [j for j, c in enumerate(calls)
            if ret[j] != c["ret"] or mp[j] != c["max_pos_out"] or not np.array_equal(aln[j], c["aln_out"])]
@@ -48,15 +54,23 @@ def test_extension_batch_matches_reference(name):
                      f"{ret[bad[0]], mp[bad[0]], aln[bad[0]]} vs {calls[bad[0]]['ret'], calls[bad[0]]['max_pos_out'], calls[bad[0]]['aln_out']}")
 
 
-@pytest.mark.parametrize("budget", [3, 40])
-def test_sliced_extensions_match_reference(budget):
-    """hsa_extend_sliced: the same calls in slices of `budget` pops -- each launch runs
-    the unfinished calls from the state their slot kept, new calls start in freed slots
-    -- must end with the reference's results."""
+@pytest.mark.parametrize("name", EXTCAP_CASES)
+def test_extension_batch_matches_reference(name):
+    check_batch(name)
+
+
+@pytest.mark.parametrize("name", EXTCAP_CASES)
+def test_extension_batch_matches_reference_buckets_in_hbm(name):
+    """The same calls with more buckets than the kernel keeps in LDS: heads and counts
+    per lane in HBM."""
+    check_batch(name, HBM_STACKS)
+
+
+def check_sliced(budget, n_stacks=None):
     from hsa_amd import _lib, index_io
     fwd, rev = index_io.read_index(INDEX["tiny"])
     gi = _lib.GpuIndex(fwd, rev, device=0)
-    calls, regimes, jobs, codes, bids = ext_batch("extcap_n4o1")
+    calls, regimes, jobs, codes, bids = ext_batch("extcap_n4o1", n_stacks)
     n_slots = 512
     todo = list(range(len(calls)))
     slot_of, resume, free = {}, {}, list(range(n_slots))
@@ -81,3 +95,17 @@ def test_sliced_extensions_match_reference(budget):
            or not np.array_equal(res[j][2], c["aln_out"])]
     assert launches > len(calls) // n_slots + 1          # slices really happened
     assert not bad, f"{len(bad)} of {len(calls)} differ; first {bad[0]}"
+
+
+@pytest.mark.parametrize("budget", [3, 40])
+def test_sliced_extensions_match_reference(budget):
+    """hsa_extend_sliced: the same calls in slices of `budget` pops -- each launch runs
+    the unfinished calls from the state their slot kept, new calls start in freed slots
+    -- must end with the reference's results."""
+    check_sliced(budget)
+
+
+def test_sliced_extensions_match_reference_buckets_in_hbm():
+    """Slices with the bucket heads and counts in HBM: the state is saved and restored
+    across launches without the copy into and out of LDS."""
+    check_sliced(3, HBM_STACKS)
