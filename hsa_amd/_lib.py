@@ -36,9 +36,15 @@ EXPORTS = [  # every symbol include/hsa_gpu.h and include/hsa_bwtaln.h declare
     "hsa_index_clone", "hsa_splice_prefetch_batch", "hsa_index_set_text", "hsa_splice_match_batch",
     "hsa_splice_device", "hsa_build_bwt_index_device64", "hsa_index_set_sa64", "hsa_index_set_sa64_device",
     "hsa_sa_position_batch64", "hsa_sa_position_device64", "hsa_psi_minus_batch64", "hsa_hit_positions_device64",
+    "hsa_index_set_text64_device", "hsa_refine_rows_device64",
 ]
 SP_RES_WORDS = 20  # hsa_splice_match_batch's per-read answer (include/hsa_gpu.h)
 ALN64_WORDS = 14   # hsa_aln64_t (include/hsa_gpu.h)
+# hsa_refine_rows_device64 (include/hsa_gpu.h): per-row status, layout limits, words per row
+HSA_RF_OK, HSA_RF_POS, HSA_RF_TEXT, HSA_RF_CAP, HSA_RF_MD = range(5)
+HSA_RF_MAX_LEN = 4095
+HSA_RF_MAX_GAP = 27
+RF_ROW_WORDS = 8
 
 
 class HsaError(RuntimeError):
@@ -132,6 +138,16 @@ class HitPosBatch64(C.Structure):
     _fields_ = [("d_n_aln", C.c_void_p), ("d_hit_off", C.c_void_p), ("d_hits", C.c_void_p), ("n_jobs", C.c_int),
                 ("max_occ", C.c_uint32), ("d_pos_off", C.c_void_p), ("d_pos", C.c_void_p), ("d_pos_hit", C.c_void_p),
                 ("pos_cap", C.c_uint64), ("d_counters", C.c_void_p)]
+
+
+class RefineBatch64(C.Structure):
+    """hsa_refine_batch64_t (include/hsa_gpu.h): the search batch and the position call's
+    outputs in, CIGAR / NM / MD per position row out, all device pointers."""
+    _fields_ = [("d_jobs", C.c_void_p), ("n_jobs", C.c_int), ("d_codes", C.c_void_p), ("d_hit_off", C.c_void_p),
+                ("d_hits", C.c_void_p), ("d_pos_off", C.c_void_p), ("d_pos", C.c_void_p), ("d_pos_hit", C.c_void_p),
+                ("pos_cap", C.c_uint64), ("d_pos_counters", C.c_void_p), ("max_len", C.c_int32),
+                ("cigar_stride", C.c_uint32), ("md_stride", C.c_uint32), ("d_rows", C.c_void_p),
+                ("d_rpos", C.c_void_p), ("d_cigar", C.c_void_p), ("d_md", C.c_void_p), ("d_counters", C.c_void_p)]
 
 
 class SeedBatch(C.Structure):
@@ -270,6 +286,9 @@ def lib():
         L.hsa_sa_position_device64.argtypes = [vp, C.c_size_t, vp, vp, vp]
         L.hsa_psi_minus_batch64.argtypes = [vp, C.c_size_t, u64, u64]
         L.hsa_hit_positions_device64.argtypes = [vp, C.POINTER(HitPosBatch64), vp]
+    if hasattr(L, "hsa_refine_rows_device64"):      # (older A/B builds lack the refinement)
+        L.hsa_index_set_text64_device.argtypes = [vp, vp, C.c_uint64]
+        L.hsa_refine_rows_device64.argtypes = [vp, C.POINTER(RefineBatch64), vp]
     if hasattr(L, "hsa_extend_batch"):
         L.hsa_extend_batch.argtypes = [vp, C.POINTER(Regime), C.c_int, vp, C.c_int, u8, i32, C.c_size_t, i32, i32,
                                        u32]
@@ -590,6 +609,22 @@ class GpuIndex:
         if max_occ is not None:
             batch.max_occ = int(max_occ)
         check(lib().hsa_hit_positions_device64(self._handle(), C.byref(batch), stream))
+
+    def set_text64_device(self, ptr, T):
+        """hsa_index_set_text64_device: the text as the 64-bit builder takes it (LSB-first
+        2-bit codes, 16 per u32) from a hipMalloc'd device array (a DeviceU64 or its
+        address), which the index owns from here on."""
+        p = ptr.ptr if isinstance(ptr, DeviceU64) else ptr
+        check(lib().hsa_index_set_text64_device(self._handle(), p, int(T)))
+        if isinstance(ptr, DeviceU64):
+            ptr.ptr = None
+
+    def refine_rows64(self, batch: "RefineBatch64", stream=None):
+        """hsa_refine_rows_device64: every position row of hit_positions64 to CIGAR, NM and
+        MD (batch.d_rows, d_rpos, d_cigar, d_md, d_counters) on `stream` (a hipStream_t
+        address; None: the index's own); does not synchronise.  hsa_amd.refine turns a
+        row's output into the SAM strings."""
+        check(lib().hsa_refine_rows_device64(self._handle(), C.byref(batch), stream))
 
     def last_pass_ms(self):
         """(k_widths ms, k_search ms) of the last device pass on this index."""

@@ -121,10 +121,10 @@ extern "C" int hsa_index_release_scratch(hsa_index_t *ix)
     (void)hipSetDevice(ix->device);
     HSA_HIP(hipStreamSynchronize(ix->stream));
     hsa_scratch_free(ix->main); hsa_scratch_free(ix->big); hsa_scratch_free(ix->huge);
-    void **bufs[] = {&ix->d_pf, &ix->d_pf2, &ix->d_sp, &ix->d_any, &ix->d_any_aux, &ix->d_help, &ix->d_hp};
+    void **bufs[] = {&ix->d_pf, &ix->d_pf2, &ix->d_sp, &ix->d_any, &ix->d_any_aux, &ix->d_help, &ix->d_hp, &ix->d_rf};
     size_t *caps[] = {&ix->d_pf_cap, &ix->d_pf2_cap, &ix->d_sp_cap, &ix->d_any_cap, &ix->d_any_aux_cap, &ix->d_help_cap,
-                      &ix->d_hp_cap};
-    for (int i = 0; i < 7; ++i) {
+                      &ix->d_hp_cap, &ix->d_rf_cap};
+    for (int i = 0; i < 8; ++i) {
         if (*bufs[i]) (void)hipFree(*bufs[i]);
         *bufs[i] = nullptr;
         *caps[i] = 0;
@@ -543,6 +543,7 @@ extern "C" int hsa_index_clone(hsa_index_t *src, hsa_index_t **out)
     ix->sa_interval = root->sa_interval; ix->n_blocks = root->n_blocks;
     ix->d_sa64 = root->d_sa64; ix->d_blocks64 = root->d_blocks64;
     ix->sa64_interval = root->sa64_interval; ix->n_blocks64 = root->n_blocks64;
+    ix->d_text64 = root->d_text64;
     ix->d_trie_w = root->d_trie_w;
     ix->trie_depth = root->trie_depth;
     ix->trie_wide = root->trie_wide; ix->trie_bytes = root->trie_bytes;
@@ -585,6 +586,7 @@ extern "C" void hsa_index_free(hsa_index_t *ix)
         ix->d_sa = ix->d_blocks = nullptr;
         ix->d_sa64 = ix->d_blocks64 = nullptr;
         ix->d_text = nullptr;
+        ix->d_text64 = nullptr;
         ix->d_trie_w = nullptr;
         ix->d_trie_s = nullptr;
     }
@@ -602,6 +604,7 @@ extern "C" void hsa_index_free(hsa_index_t *ix)
     (void)hipFree(ix->d_in); (void)hipFree(ix->d_out); (void)hipFree(ix->d_ctr); (void)hipFree(ix->d_wrows); (void)hipFree(ix->d_ovf); (void)hipFree(ix->d_seed); (void)hipFree(ix->d_ext); (void)hipFree(ix->d_slices);
     (void)hipFree(ix->d_sa); (void)hipFree(ix->d_blocks); (void)hipFree(ix->d_text);
     (void)hipFree(ix->d_sa64); (void)hipFree(ix->d_blocks64); (void)hipFree(ix->d_hp);
+    (void)hipFree(ix->d_text64); (void)hipFree(ix->d_rf);
     if (ix->d_sp) (void)hipFree(ix->d_sp);
     (void)hipFree(ix->d_trie_w);
     (void)hipFree(ix->d_trie_s);

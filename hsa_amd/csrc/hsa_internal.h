@@ -107,6 +107,11 @@ struct hsa_index {
     uint32_t *d_text = nullptr;
     uint64_t text_words = 0;
     uint32_t dna_len = 0;
+    // the text of a 64-bit index (hsa_index_set_text64_device): LSB-first, 16 codes per
+    // u32, T64 characters; owned by the index, shared with its clones.  d_rf:
+    // hsa_refine_rows_device64's row list and per-wave traceback scratch
+    uint32_t *d_text64 = nullptr;
+    void *d_rf = nullptr; size_t d_rf_cap = 0;
     // the splice path's kernel (hsa_splice.hip): per-lane state, stacks, buffers
     void *d_sp = nullptr; size_t d_sp_cap = 0;
     uint64_t *d_ctr = nullptr;

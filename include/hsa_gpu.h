@@ -25,6 +25,9 @@
  *                         (2BWT-Interface.c:329).
  *   hsa_sa_position_*64, hsa_hit_positions_device64 -- the same on a 64-bit index (texts
  *                         of 2^32 characters or more), which the reference cannot hold.
+ *   hsa_refine_rows_device64 -- refine_gapped_core and bwa_cal_md1 (bwtse.c:380-494) with
+ *                         aln_global_core (stdaln.c:345-525) for the position rows of a 64-bit
+ *                         index: CIGAR, NM and MD.
  *   hsa_extend_batch   -- bwt_extend_backward / bwt_extend_foreward (bwtgap.c:640-663,
  *                         bwt_backtracing_search :346-511): the splice path's seed
  *                         extensions.
@@ -481,8 +484,9 @@ int hsa_build_bwt_device64(int device, uint64_t T, const uint32_t *d_text_lsb, i
 /* ---- text positions on the 64-bit path ----
  * SA index -> text position for an index made by hsa_index_create_device64, of any
  * length under 2^36 (no reference counterpart: the reference ends at 2^32 - 1
- * characters).  Not built: a 64-bit splice path or SAM stage, and an on-disk format for
- * 64-bit samples (the .sa file's values are u32).
+ * characters).  CIGAR, NM and MD of the position rows: hsa_refine_rows_device64 below.
+ * Not built: a 64-bit splice path, and an on-disk format for 64-bit samples (the .sa
+ * file's values are u32).
  *
  * hsa_build_bwt_index_device64: hsa_build_bwt_index_device for any 1 <= T < 2^36, with
  * u64 samples: d_sa64[r / sa_interval] = SA[r] for every row r > 0 with r % sa_interval
@@ -549,6 +553,86 @@ typedef struct {
     uint64_t *d_counters;     /* >= 4 u64: [0] rows wanted, [1] rows written, [2] walks cut by the bound */
 } hsa_hitpos_batch64_t;
 int hsa_hit_positions_device64(hsa_index_t *ix, const hsa_hitpos_batch64_t *b, void *stream);
+
+/* ---- position rows to CIGAR, NM and MD on the 64-bit path ----
+ * refine_gapped_core (bwtse.c:380-440) with its banded global alignment
+ * (aln_global_core with aln_param_bwa, stdaln.c:227, :345-525; aln_path2cigar32 :1010)
+ * and bwa_cal_md1 (bwtse.c:442-494), for every row hsa_hit_positions_device64 wrote.
+ *
+ * The text.  hsa_index_set_text64_device attaches it as the 64-bit builder takes it:
+ * 2-bit codes, LSB-first, 16 per u32, ceil(T / 16) words of device memory (hipMalloc'd),
+ * T the index's length (HSA_E_ARG otherwise).  The handle takes ownership; only on an
+ * index of hsa_index_create_device64, refused on a clone and on an index with live
+ * clones, as hsa_index_set_sa64_device; clones share the array, the last free releases
+ * it, and on an error the array stays the caller's.  An index under 2^32 characters that
+ * has the host's packed text (hsa_index_set_text) is served from that array when no
+ * 64-bit text is attached. */
+int hsa_index_set_text64_device(hsa_index_t *ix, uint32_t *d_text_lsb, uint64_t T);
+
+/* Per-row status: a row is answered exactly (HSA_RF_OK) or refused, never approximated. */
+#define HSA_RF_OK    0u
+#define HSA_RF_POS   1u   /* the position row is all-ones (no block, or a walk cut by the bound) */
+#define HSA_RF_TEXT  2u   /* the ungapped compare would read past the text (the reference has no
+                             bound at bwtse.c:480-482), or a gapped row starts at or past its end
+                             (an empty window: the reference dereferences a NULL CIGAR) */
+#define HSA_RF_CAP   3u   /* the read or the gap is past the kernel's layout */
+#define HSA_RF_MD    4u   /* the CIGAR or the MD string did not fit its stride: n_cigar and md_len
+                             hold the needed lengths, the arrays their first stride entries */
+/* The layout: every row with len <= the batch's max_len (at most HSA_RF_MAX_LEN) and
+ * n_gapo + n_gape <= HSA_RF_MAX_GAP is answered; HSA_RF_CAP is only for rows past that. */
+#define HSA_RF_MAX_LEN 4095
+#define HSA_RF_MAX_GAP 27
+#define HSA_RF_ROW_WORDS 8
+/* Row t (the position call's row t) gets
+ *   d_rows + 8 t   status, n_cigar, NM, md_len, ref bases dropped at the 5' end, at the 3' end
+ *                  (the reference's *start += / *end -= adjustments, bwtse.c:417, :424:
+ *                  reported, the caller applies them), two zero words;
+ *   d_rpos + 2 t   the refined text position and 1-based position in the chromosome: a
+ *                  leading deletion's length is added to both without a new block lookup,
+ *                  as bwtse.c:413-417 does;
+ *   d_cigar + cigar_stride t   the ops as bwa_cigar_t (bwtaln.h:70-80: op << 28 | len,
+ *                  op 0 M, 1 I, 2 D, 4 S);
+ *   d_md + md_stride t         the MD string's bytes (md_len of them, no terminator).
+ * A row's gap count is its record's n_gapo + n_gape (bwtse.c:89, :561).  Gap 0: no
+ * alignment; the CIGAR is one `len`M op (a difference from the reference, which keeps a NULL
+ * CIGAR there and prints "<len>M"), MD and NM from bwa_cal_md1's no-gap branch.  Gap > 0:
+ * the window is len + gap text characters from the row's position, cut at the text's end
+ * (:391-394); end deletions are stripped and end insertions become S (:413-434); MD and NM
+ * from the CIGAR branch.  The read handed to the alignment is the reference's
+ * `strand ? rseq : seq` (:554): d_codes as they are for strand 0, their reverse complement
+ * for strand 1 (bwaseqio.c:212-215 with the complement the aligner's default mode sets).
+ * Rows other than HSA_RF_OK / HSA_RF_MD get zero lengths and their position unrefined.
+ *
+ * Inputs are the search batch (d_jobs, d_codes, d_hit_off, d_hits as hsa_aln64_t) and the
+ * position call's outputs as they sit on the device; the row count is
+ * min(d_pos_off[n_jobs], pos_cap, d_pos_counters[1]) (d_pos_counters may be NULL), read on
+ * the device: no host round trip.  d_counters (>= 8 u64, zeroed by the call): [0] rows,
+ * [1 + s] rows of status s (s = 0..4), [6] rows that ran the alignment, [7] unused.
+ * Two launches on `stream` (NULL = the library's); the call does not synchronise.
+ * Needs a text (above); scratch grows on the handle (hsa_index_release_scratch).
+ *
+ * Not built, and left to the caller: hit choice and mapQ (bwt_aln2seq_core,
+ * bwtse.c:21-113, consumes the process-wide drand48 sequence in read order; every row the
+ * position call produced is refined, which is what XA lists need), bwa_correct_trimmed
+ * (:496-534, needs full_len, which the device batch does not carry), spliced reads (N ops,
+ * :562-619), a 32-bit-record (bwt_aln1_t) variant, and an on-disk format for 64-bit
+ * samples.  The drop-in's SAM stage keeps the host's bwa_refine_gapped. */
+typedef struct {
+    const hsa_job_t *d_jobs; int n_jobs;
+    const uint8_t *d_codes;
+    const uint64_t *d_hit_off; const uint32_t *d_hits;       /* the search's: hsa_aln64_t */
+    const uint64_t *d_pos_off; const uint64_t *d_pos; const uint32_t *d_pos_hit;
+    uint64_t pos_cap;                /* rows the position arrays and the outputs hold */
+    const uint64_t *d_pos_counters;  /* the position call's counters, or NULL */
+    int32_t max_len;                 /* longest read of the batch: sizes the scratch */
+    uint32_t cigar_stride, md_stride; /* ops / bytes per row */
+    uint32_t *d_rows;                /* HSA_RF_ROW_WORDS u32 per row */
+    uint64_t *d_rpos;                /* 2 u64 per row */
+    uint32_t *d_cigar;
+    uint8_t *d_md;
+    uint64_t *d_counters;            /* >= 8 u64 */
+} hsa_refine_batch64_t;
+int hsa_refine_rows_device64(hsa_index_t *ix, const hsa_refine_batch64_t *b, void *stream);
 
 #ifdef __cplusplus
 }
