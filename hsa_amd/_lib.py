@@ -36,7 +36,8 @@ EXPORTS = [  # every symbol include/hsa_gpu.h and include/hsa_bwtaln.h declare
     "hsa_index_clone", "hsa_splice_prefetch_batch", "hsa_index_set_text", "hsa_splice_match_batch",
     "hsa_splice_device", "hsa_build_bwt_index_device64", "hsa_index_set_sa64", "hsa_index_set_sa64_device",
     "hsa_sa_position_batch64", "hsa_sa_position_device64", "hsa_psi_minus_batch64", "hsa_hit_positions_device64",
-    "hsa_index_set_text64_device", "hsa_refine_rows_device64",
+    "hsa_index_set_text64_device", "hsa_refine_rows_device64", "hsa_choose_hits_device64",
+    "hsa_choose_timing", "hsa_choose_launch_times",
 ]
 SP_RES_WORDS = 20  # hsa_splice_match_batch's per-read answer (include/hsa_gpu.h)
 ALN64_WORDS = 14   # hsa_aln64_t (include/hsa_gpu.h)
@@ -45,6 +46,9 @@ HSA_RF_OK, HSA_RF_POS, HSA_RF_TEXT, HSA_RF_CAP, HSA_RF_MD = range(5)
 HSA_RF_MAX_LEN = 4095
 HSA_RF_MAX_GAP = 27
 RF_ROW_WORDS = 8
+# hsa_choose_hits_device64: glibc's drand48 state in a process that never seeds; read types
+DRAND48_SEED0 = 0
+CHOOSE_NONE, CHOOSE_UNIQUE, CHOOSE_REPEAT = range(3)
 
 
 class HsaError(RuntimeError):
@@ -150,6 +154,22 @@ class RefineBatch64(C.Structure):
                 ("d_rpos", C.c_void_p), ("d_cigar", C.c_void_p), ("d_md", C.c_void_p), ("d_counters", C.c_void_p)]
 
 
+class ChooseBatch64(C.Structure):
+    """hsa_choose_batch64_t (include/hsa_gpu.h): the search's hit lists in; each read's
+    chosen record, SA row, mapQ, X0 / X1 and generator state, and the chosen and XA rows in
+    hit_positions64's layout out, all device pointers."""
+    _fields_ = [("d_jobs", C.c_void_p), ("n_jobs", C.c_int), ("d_n_aln", C.c_void_p), ("d_hit_off", C.c_void_p),
+                ("d_hits", C.c_void_p), ("n_multi", C.c_uint32), ("rng_state", C.c_uint64), ("d_log_n", C.c_void_p),
+                ("d_sel", C.c_void_p), ("d_sel64", C.c_void_p), ("d_rng_out", C.c_void_p), ("d_pos_off", C.c_void_p),
+                ("d_pos", C.c_void_p), ("d_pos_hit", C.c_void_p), ("pos_cap", C.c_uint64), ("d_counters", C.c_void_p)]
+
+
+def log_n_table() -> np.ndarray:
+    """g_log_n (bwtse.c:838-842): (int)(4.343 * log(i) + 0.5) for i = 1..255, [0] = 0."""
+    import math
+    return np.array([0] + [int(4.343 * math.log(i) + 0.5) for i in range(1, 256)], np.int32)
+
+
 class SeedBatch(C.Structure):
     """hsa_seed_batch_t (include/hsa_gpu.h): the splice seeds of a device batch."""
     _fields_ = [("d_jobs", C.c_void_p), ("n_jobs", C.c_int), ("d_codes", C.c_void_p), ("d_flags", C.c_void_p),
@@ -222,6 +242,7 @@ def lib():
     i32 = np.ctypeslib.ndpointer(np.int32, flags="C")
     u8 = np.ctypeslib.ndpointer(np.uint8, flags="C")
     vp = C.c_void_p
+    f32 = np.ctypeslib.ndpointer(np.float32, flags="C")
     L.hsa_device_count.restype = C.c_int
     L.hsa_last_error.restype = C.c_char_p
     L.hsa_index_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, u32, u32, C.c_uint32, C.c_uint32, u32, u32,
@@ -289,13 +310,17 @@ def lib():
     if hasattr(L, "hsa_refine_rows_device64"):      # (older A/B builds lack the refinement)
         L.hsa_index_set_text64_device.argtypes = [vp, vp, C.c_uint64]
         L.hsa_refine_rows_device64.argtypes = [vp, C.POINTER(RefineBatch64), vp]
+    if hasattr(L, "hsa_choose_hits_device64"):      # (older A/B builds lack the choice)
+        L.hsa_choose_hits_device64.argtypes = [vp, C.POINTER(ChooseBatch64), vp]
+        L.hsa_choose_timing.argtypes = [C.c_int]
+        L.hsa_choose_timing.restype = None
+        L.hsa_choose_launch_times.argtypes = [vp, f32]
     if hasattr(L, "hsa_extend_batch"):
         L.hsa_extend_batch.argtypes = [vp, C.POINTER(Regime), C.c_int, vp, C.c_int, u8, i32, C.c_size_t, i32, i32,
                                        u32]
     if hasattr(L, "hsa_extend_sliced"):
         L.hsa_extend_sliced.argtypes = [vp, C.POINTER(Regime), C.c_int, vp, i32, u8, C.c_int, u8, i32, C.c_size_t,
                                         C.c_int, C.c_uint32, i32, i32, u32]
-    f32 = np.ctypeslib.ndpointer(np.float32, flags="C")
     L.hsa_pass_times.argtypes = [vp, C.c_int, f32, f32]
     if hasattr(L, "hsa_cal_sa_reg_gap_multi"):      # (older A/B builds lack it)
         L.hsa_cal_sa_reg_gap_multi.restype = C.c_long
@@ -474,6 +499,9 @@ class GpuIndex:
         if getattr(self, "h", None):
             lib().hsa_index_free(self.h)
             self.h = None
+        if getattr(self, "_log_n", None) is not None:
+            self._log_n.free()
+            self._log_n = None
 
     def __del__(self):
         try:
@@ -625,6 +653,33 @@ class GpuIndex:
         address; None: the index's own); does not synchronise.  hsa_amd.refine turns a
         row's output into the SAM strings."""
         check(lib().hsa_refine_rows_device64(self._handle(), C.byref(batch), stream))
+
+    def choose_hits64(self, batch: "ChooseBatch64", stream=None):
+        """hsa_choose_hits_device64: each read's hit as the reference chooses it (the
+        drand48 sequence from batch.rng_state, in read order), mapQ, X0 / X1 and the chosen
+        and XA rows (batch.d_sel, d_sel64, d_rng_out, d_pos_off, d_pos, d_pos_hit,
+        d_counters) on `stream` (a hipStream_t address; None: the index's own); does not
+        synchronise.  A batch without d_log_n gets the index's own copy of log_n_table().
+        refine_rows64 takes the rows as it takes hit_positions64's; hsa_amd.sam formats the
+        line."""
+        if not hasattr(lib(), "hsa_choose_hits_device64"):
+            raise HsaError("this libhsa_gpu.so has no hsa_choose_hits_device64: rebuild it")
+        if not batch.d_log_n:
+            if getattr(self, "_log_n", None) is None:
+                t = log_n_table()
+                self._log_n = DeviceU64(len(t) // 2)
+                self._log_n.write(0, t.view(np.uint64))
+            batch.d_log_n = self._log_n.ptr
+        check(lib().hsa_choose_hits_device64(self._handle(), C.byref(batch), stream))
+
+    CHOOSE_LAUNCHES = ("class", "scan", "compact", "maps", "walk", "pick", "rows")
+
+    def choose_launch_times(self) -> dict:
+        """hsa_choose_launch_times: ms per launch of this handle's last choose_hits64 call
+        made after lib().hsa_choose_timing(1); waits for it."""
+        ms = np.zeros(len(self.CHOOSE_LAUNCHES), np.float32)
+        check(lib().hsa_choose_launch_times(self._handle(), ms))
+        return {k: float(v) for k, v in zip(self.CHOOSE_LAUNCHES, ms)}
 
     def last_pass_ms(self):
         """(k_widths ms, k_search ms) of the last device pass on this index."""

@@ -121,10 +121,11 @@ extern "C" int hsa_index_release_scratch(hsa_index_t *ix)
     (void)hipSetDevice(ix->device);
     HSA_HIP(hipStreamSynchronize(ix->stream));
     hsa_scratch_free(ix->main); hsa_scratch_free(ix->big); hsa_scratch_free(ix->huge);
-    void **bufs[] = {&ix->d_pf, &ix->d_pf2, &ix->d_sp, &ix->d_any, &ix->d_any_aux, &ix->d_help, &ix->d_hp, &ix->d_rf};
+    void **bufs[] = {&ix->d_pf, &ix->d_pf2, &ix->d_sp, &ix->d_any, &ix->d_any_aux, &ix->d_help, &ix->d_hp, &ix->d_rf,
+                     &ix->d_ch};
     size_t *caps[] = {&ix->d_pf_cap, &ix->d_pf2_cap, &ix->d_sp_cap, &ix->d_any_cap, &ix->d_any_aux_cap, &ix->d_help_cap,
-                      &ix->d_hp_cap, &ix->d_rf_cap};
-    for (int i = 0; i < 8; ++i) {
+                      &ix->d_hp_cap, &ix->d_rf_cap, &ix->d_ch_cap};
+    for (int i = 0; i < 9; ++i) {
         if (*bufs[i]) (void)hipFree(*bufs[i]);
         *bufs[i] = nullptr;
         *caps[i] = 0;
@@ -604,7 +605,7 @@ extern "C" void hsa_index_free(hsa_index_t *ix)
     (void)hipFree(ix->d_in); (void)hipFree(ix->d_out); (void)hipFree(ix->d_ctr); (void)hipFree(ix->d_wrows); (void)hipFree(ix->d_ovf); (void)hipFree(ix->d_seed); (void)hipFree(ix->d_ext); (void)hipFree(ix->d_slices);
     (void)hipFree(ix->d_sa); (void)hipFree(ix->d_blocks); (void)hipFree(ix->d_text);
     (void)hipFree(ix->d_sa64); (void)hipFree(ix->d_blocks64); (void)hipFree(ix->d_hp);
-    (void)hipFree(ix->d_text64); (void)hipFree(ix->d_rf);
+    (void)hipFree(ix->d_text64); (void)hipFree(ix->d_rf); (void)hipFree(ix->d_ch);
     if (ix->d_sp) (void)hipFree(ix->d_sp);
     (void)hipFree(ix->d_trie_w);
     (void)hipFree(ix->d_trie_s);
@@ -612,6 +613,8 @@ extern "C" void hsa_index_free(hsa_index_t *ix)
     if (ix->ev1) (void)hipEventDestroy(ix->ev1);
     if (ix->evm) (void)hipEventDestroy(ix->evm);
     if (ix->ev_sp) (void)hipEventDestroy(ix->ev_sp);
+    for (int i = 0; i <= HSA_CH_LAUNCHES; ++i)
+        if (ix->ch_ev[i]) (void)hipEventDestroy(ix->ch_ev[i]);
     for (int i = 0; i < hsa_index::PASS_RING; ++i)
         for (int j = 0; j < 3; ++j)
             if (ix->pev[i][j]) (void)hipEventDestroy(ix->pev[i][j]);

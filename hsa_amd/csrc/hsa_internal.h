@@ -112,6 +112,10 @@ struct hsa_index {
     // hsa_refine_rows_device64's row list and per-wave traceback scratch
     uint32_t *d_text64 = nullptr;
     void *d_rf = nullptr; size_t d_rf_cap = 0;
+    // hsa_choose_hits_device64: per-read classes and their scan, the variable reads' list
+    void *d_ch = nullptr; size_t d_ch_cap = 0;
+    hipEvent_t ch_ev[HSA_CH_LAUNCHES + 1] = {};    // around its launches (hsa_choose_timing)
+    bool ch_timed = false;
     // the splice path's kernel (hsa_splice.hip): per-lane state, stacks, buffers
     void *d_sp = nullptr; size_t d_sp_cap = 0;
     uint64_t *d_ctr = nullptr;
@@ -158,6 +162,9 @@ int hsa_realloc_device(void **out, void **old, size_t bytes);
 SaView hsa_sa_view(const hsa_index *ix);
 // The 64-bit view (hsa_index_set_sa64); max_walk: HSA_SA_MAX_WALK as read at the call
 SaView64 hsa_sa_view64(const hsa_index *ix, uint32_t max_walk);
+uint32_t hsa_sa_max_walk();                                // HSA_SA_MAX_WALK, read at each call
+// HSA_E_ARG unless the index is one of hsa_index_create_device64 with hsa_index_set_sa64's arrays
+int hsa_need_sa64(const hsa_index *ix, const char *what);
 
 // The splice prefetch's device outputs (pf_dev, hsa_splice_prefetch.h), as the splice
 // path's kernel reads them (hsa_splice.hip).

@@ -86,6 +86,16 @@ struct SaView64 {
 };
 
 #define HSA_SA64_NONE 0xFFFFFFFFFFFFFFFFull
+#define HSA_ALN64_WORDS 14u                    // hsa_aln64_t: k at words 2-3, l at words 4-5
+
+// rows k .. l of a hit record of the 64-bit search (none for a malformed one)
+__device__ __forceinline__ uint64_t hsa_aln64_rows(const uint32_t *__restrict__ rec, uint64_t &k)
+{
+    const uint2 kw = *reinterpret_cast<const uint2 *>(rec + 2), lw = *reinterpret_cast<const uint2 *>(rec + 4);
+    k = (uint64_t)kw.x | ((uint64_t)kw.y << 32);
+    const uint64_t l = (uint64_t)lw.x | ((uint64_t)lw.y << 32);
+    return l >= k ? l - k + 1u : 0u;
+}
 
 // index % interval without a 64-bit division where the interval is a power of two (a
 // uniform branch: the usual intervals are)

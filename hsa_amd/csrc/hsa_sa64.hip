@@ -25,9 +25,8 @@
 #include "hsa_sa.h"
 
 #define HSA_SA_MAX_WALK_DEFAULT (1u << 22)
-#define HSA_ALN64_WORDS 14u                    // hsa_aln64_t: k at words 2-3, l at words 4-5
 
-static uint32_t sa_max_walk()
+uint32_t hsa_sa_max_walk()
 {
     const char *e = getenv("HSA_SA_MAX_WALK");
     if (!e || !*e) return HSA_SA_MAX_WALK_DEFAULT;
@@ -79,7 +78,7 @@ static int need_wide(const hsa_index *ix, const char *what)
     return 0;
 }
 
-static int need_sa64(const hsa_index *ix, const char *what)
+int hsa_need_sa64(const hsa_index *ix, const char *what)
 {
     if (int rc = need_wide(ix, what)) return rc;
     if (!ix->d_sa64) { hsa_set_error("%s: no suffix array attached (hsa_index_set_sa64)", what); return HSA_E_ARG; }
@@ -141,12 +140,12 @@ extern "C" int hsa_index_set_sa64_device(hsa_index_t *ix, uint64_t *d_sa_values,
 
 extern "C" int hsa_sa_position_device64(hsa_index_t *ix, size_t n, const uint64_t *d_idx, uint64_t *d_out4, void *stream)
 {
-    if (int rc = need_sa64(ix, "hsa_sa_position_device64")) return rc;
+    if (int rc = hsa_need_sa64(ix, "hsa_sa_position_device64")) return rc;
     if (n && (!d_idx || !d_out4)) { hsa_set_error("hsa_sa_position_device64: null argument"); return HSA_E_ARG; }
     if ((n + 255) / 256 > 0x7FFFFFFFull) { hsa_set_error("hsa_sa_position_device64: too many indices"); return HSA_E_ARG; }
     HSA_HIP(hipSetDevice(ix->device));
     Sa64Args A;
-    A.v = hsa_sa_view64(ix, sa_max_walk());
+    A.v = hsa_sa_view64(ix, hsa_sa_max_walk());
     A.idx = d_idx; A.out = d_out4; A.n = n;
     hipStream_t st = stream ? (hipStream_t)stream : ix->stream;
     if (n) hipLaunchKernelGGL(k_sa_position64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A);
@@ -156,7 +155,7 @@ extern "C" int hsa_sa_position_device64(hsa_index_t *ix, size_t n, const uint64_
 
 extern "C" int hsa_sa_position_batch64(hsa_index_t *ix, size_t n, const uint64_t *sa_index, uint64_t *out4)
 {
-    if (int rc = need_sa64(ix, "hsa_sa_position_batch64")) return rc;
+    if (int rc = hsa_need_sa64(ix, "hsa_sa_position_batch64")) return rc;
     if (n && (!sa_index || !out4)) { hsa_set_error("hsa_sa_position_batch64: null argument"); return HSA_E_ARG; }
     int rc;
     if ((rc = hsa_grow(&ix->d_in, &ix->d_in_cap, n * 8 + 64)) || (rc = hsa_grow(&ix->d_out, &ix->d_out_cap, n * 32 + 64)))
@@ -210,15 +209,6 @@ struct HitPosArgs {
     unsigned long long *ctr;
 };
 
-// rows k .. l of a hit record (none for a malformed one)
-__device__ __forceinline__ uint64_t hitpos_rows(const uint32_t *__restrict__ rec, uint64_t &k)
-{
-    const uint2 kw = *reinterpret_cast<const uint2 *>(rec + 2), lw = *reinterpret_cast<const uint2 *>(rec + 4);
-    k = (uint64_t)kw.x | ((uint64_t)kw.y << 32);
-    const uint64_t l = (uint64_t)lw.x | ((uint64_t)lw.y << 32);
-    return l >= k ? l - k + 1u : 0u;
-}
-
 // counts[j]: the rows of read j, at most max_occ; counts[n_jobs] = 0 (the scan's last slot)
 __global__ void __launch_bounds__(256) k_hitpos_count(HitPosArgs a, uint64_t *counts)
 {
@@ -230,7 +220,7 @@ __global__ void __launch_bounds__(256) k_hitpos_count(HitPosArgs a, uint64_t *co
         const uint32_t *rec = a.hits + a.hit_off[j] * HSA_ALN64_WORDS;
         for (int32_t i = 0; i < na && n < a.max_occ; ++i, rec += HSA_ALN64_WORDS) {
             uint64_t k;
-            n += hitpos_rows(rec, k);
+            n += hsa_aln64_rows(rec, k);
         }
         if (n > a.max_occ) n = a.max_occ;
     }
@@ -257,7 +247,7 @@ __global__ void __launch_bounds__(256, 8) k_hitpos_rows(HitPosArgs a)
     uint64_t k = 0;
     int32_t i = 0;
     for (; i < na; ++i, rec += HSA_ALN64_WORDS) {
-        const uint64_t n = hitpos_rows(rec, k);
+        const uint64_t n = hsa_aln64_rows(rec, k);
         if (rest < n) break;
         rest -= n;
     }
@@ -268,7 +258,7 @@ __global__ void __launch_bounds__(256, 8) k_hitpos_rows(HitPosArgs a)
 
 extern "C" int hsa_hit_positions_device64(hsa_index_t *ix, const hsa_hitpos_batch64_t *b, void *stream)
 {
-    if (int rc = need_sa64(ix, "hsa_hit_positions_device64")) return rc;
+    if (int rc = hsa_need_sa64(ix, "hsa_hit_positions_device64")) return rc;
     if (!b || b->n_jobs < 0 || b->max_occ == 0 || !b->d_pos_off || !b->d_counters ||
         (b->n_jobs && (!b->d_n_aln || !b->d_hit_off || !b->d_hits)) || (b->pos_cap && (!b->d_pos || !b->d_pos_hit))) {
         hsa_set_error("hsa_hit_positions_device64: bad arguments");
@@ -288,7 +278,7 @@ extern "C" int hsa_hit_positions_device64(hsa_index_t *ix, const hsa_hitpos_batc
     uint64_t *d_cnt = (uint64_t *)ix->d_hp;
     void *d_tmp = (char *)ix->d_hp + cnt_bytes;
     HitPosArgs A;
-    A.v = hsa_sa_view64(ix, sa_max_walk());
+    A.v = hsa_sa_view64(ix, hsa_sa_max_walk());
     A.n_aln = b->d_n_aln; A.hit_off = b->d_hit_off; A.hits = b->d_hits;
     A.n_jobs = (uint32_t)n; A.max_occ = b->max_occ;
     A.pos_off = b->d_pos_off; A.pos = b->d_pos; A.pos_hit = b->d_pos_hit; A.pos_cap = b->pos_cap;

@@ -484,7 +484,8 @@ int hsa_build_bwt_device64(int device, uint64_t T, const uint32_t *d_text_lsb, i
 /* ---- text positions on the 64-bit path ----
  * SA index -> text position for an index made by hsa_index_create_device64, of any
  * length under 2^36 (no reference counterpart: the reference ends at 2^32 - 1
- * characters).  CIGAR, NM and MD of the position rows: hsa_refine_rows_device64 below.
+ * characters).  CIGAR, NM and MD of the position rows: hsa_refine_rows_device64 below;
+ * hit choice, mapQ and the XA rows: hsa_choose_hits_device64 below.
  * Not built: a 64-bit splice path, and an on-disk format for 64-bit samples (the .sa
  * file's values are u32).
  *
@@ -611,12 +612,13 @@ int hsa_index_set_text64_device(hsa_index_t *ix, uint32_t *d_text_lsb, uint64_t 
  * Two launches on `stream` (NULL = the library's); the call does not synchronise.
  * Needs a text (above); scratch grows on the handle (hsa_index_release_scratch).
  *
- * Not built, and left to the caller: hit choice and mapQ (bwt_aln2seq_core,
- * bwtse.c:21-113, consumes the process-wide drand48 sequence in read order; every row the
- * position call produced is refined, which is what XA lists need), bwa_correct_trimmed
- * (:496-534, needs full_len, which the device batch does not carry), spliced reads (N ops,
- * :562-619), a 32-bit-record (bwt_aln1_t) variant, and an on-disk format for 64-bit
- * samples.  The drop-in's SAM stage keeps the host's bwa_refine_gapped. */
+ * The rows may be hsa_hit_positions_device64's (every row up to max_occ) or
+ * hsa_choose_hits_device64's (below: the chosen row and the XA rows, same layout).
+ *
+ * Not built, and left to the caller: bwa_correct_trimmed (:496-534, needs full_len, which
+ * the device batch does not carry), spliced reads (N ops, :562-619), a 32-bit-record
+ * (bwt_aln1_t) variant, and an on-disk format for 64-bit samples.  The drop-in's SAM stage
+ * keeps the host's bwa_refine_gapped. */
 typedef struct {
     const hsa_job_t *d_jobs; int n_jobs;
     const uint8_t *d_codes;
@@ -633,6 +635,81 @@ typedef struct {
     uint64_t *d_counters;            /* >= 8 u64 */
 } hsa_refine_batch64_t;
 int hsa_refine_rows_device64(hsa_index_t *ix, const hsa_refine_batch64_t *b, void *stream);
+
+/* ---- each read's hit, mapQ and XA rows on the 64-bit path ----
+ * bwt_aln2seq_core(p, 1, n_multi) (bwtse.c:21-113; the reference calls it with n_multi 3,
+ * bwtaln.c:514), the multi-row filter of bwa_cal_pac_pos (:360-366) and bwa_approx_mapQ
+ * (:122-131) for the hit lists of hsa_search_device64 as they sit on the device; search ->
+ * choose -> refine gives, without a host round trip, what bwa_print_sam1 prints for an
+ * unspliced single-end read.
+ *
+ * The draws.  The reference picks among a read's equal-best records with the process-wide
+ * drand48 sequence, consumed in read order.  rng_state is the generator's 48-bit state
+ * before read 0 (HSA_DRAND48_SEED0 in a process that never seeds, as the reference: glibc
+ * starts from X = 0, not from the 0x1234ABCD330E of the SVID text);
+ * *d_rng_out is the state after the last read.  A sub-range [s, e) of a batch is served by
+ * passing d_jobs + s, d_n_aln + s, d_hit_off + s (d_hits as it is), n_jobs = e - s, the
+ * outputs offset the same way (d_sel + 4 s, d_sel64 + 4 s; the row arrays start at 0 for
+ * every call) and the state the call for [0, s) left: calls chained like this give what
+ * one call gives, and the reference's batches of 0x40000 reads chain the same way.
+ *
+ * Outputs, all in read order (two runs give equal arrays):
+ *   d_sel + 4 j    type (0 no hit: n_aln <= 0; 1 unique; 2 repeat), index of the chosen
+ *                  record in the read's list, mapQ (with the job's max_diff), XA rows;
+ *   d_sel64 + 4 j  the chosen SA row, c1 (rows of the equal-best records: X0), c2 (rows of
+ *                  the others: X1), the generator's state at the start of the read;
+ *   d_pos_off, d_pos, d_pos_hit (pos_cap rows): the layout of hsa_hit_positions_device64,
+ *                  which hsa_refine_rows_device64 takes unchanged.  A read with a hit has
+ *                  one row, or, when its records hold n <= n_multi + 1 rows in all, n rows:
+ *                  row 0 the chosen SA row, rows 1.. the others in list order, k .. l
+ *                  ascending (the reference drops the multi row at the main row's position,
+ *                  and distinct SA rows have distinct positions).  d_pos_hit: the row's
+ *                  record.  No draw is made for them (bwtse.c:93-108 cannot be reached).
+ * d_counters (>= 8 u64, zeroed by the call): [0] rows wanted, [1] rows written (rows past
+ * pos_cap are not written: run again with more room), [2] walks cut by HSA_SA_MAX_WALK,
+ * [3] reads with a hit, [4] repeat reads, [5] reads whose draws were walked in order (two
+ * or more equal-best records), [6] zero-draw reads, [7] the lowest of them (all-ones: none).
+ *
+ * The zero-draw read.  A read with one equal-best record makes two draws unless the first
+ * is exactly 0 (probability 2^-48), when bwtse.c:44 is false and it makes one.  The states
+ * are computed for two.  Such a read is counted in [6]: it keeps the reference's zeroed
+ * fields (record 0, SA row 0; its other rows omit the read's first row), the states of the
+ * reads after it and *d_rng_out are NOT the sequential ones, and the caller re-runs from
+ * read [7] + 1 with the successor of d_sel64[4 * [7] + 3] (one draw) as the state.  All other values are
+ * the sequential walk's for every input (64-bit k, l, counts: the reference's wherever its
+ * 32-bit arithmetic does not wrap).
+ *
+ * d_log_n: 256 int32 on the device, g_log_n[i] = (int)(4.343 * log(i) + 0.5), [0] unused
+ * (bwtse.c:841; computed on the host so that no device log enters).  d_sel, d_sel64 and
+ * d_hits 16-, 16- and 8-byte aligned.  Needs hsa_index_set_sa64's arrays (HSA_E_ARG
+ * otherwise, as for null pointers and a state of 2^48 or more).  Six kernels and a scan
+ * on `stream` (NULL = the library's); the call does not synchronise; scratch grows on the
+ * handle (hsa_index_release_scratch). */
+#define HSA_DRAND48_SEED0 0ull
+typedef struct {
+    const hsa_job_t *d_jobs; int n_jobs;
+    const int32_t *d_n_aln; const uint64_t *d_hit_off; const uint32_t *d_hits;   /* hsa_aln64_t */
+    uint32_t n_multi;
+    uint64_t rng_state;
+    const int32_t *d_log_n;
+    uint32_t *d_sel;          /* 4 u32 per read */
+    uint64_t *d_sel64;        /* 4 u64 per read */
+    uint64_t *d_rng_out;      /* 1 u64 */
+    uint64_t *d_pos_off;      /* n_jobs + 1 */
+    uint64_t *d_pos;          /* 4 u64 per row */
+    uint32_t *d_pos_hit;
+    uint64_t pos_cap;
+    uint64_t *d_counters;     /* >= 8 u64 */
+} hsa_choose_batch64_t;
+int hsa_choose_hits_device64(hsa_index_t *ix, const hsa_choose_batch64_t *b, void *stream);
+/* Probes: hsa_choose_timing(1) makes every later call record events around its launches
+ * (process-wide; off by default: nothing is recorded), and hsa_choose_launch_times waits
+ * for the handle's last timed call and gives the HSA_CH_LAUNCHES times in ms: the class
+ * kernel (with the counters' memset), the scan, the compaction, the maps, the one-wave
+ * walk, the choice, the rows. */
+#define HSA_CH_LAUNCHES 7
+void hsa_choose_timing(int on);
+int hsa_choose_launch_times(hsa_index_t *ix, float *ms);
 
 #ifdef __cplusplus
 }
