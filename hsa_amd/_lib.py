@@ -37,7 +37,8 @@ EXPORTS = [  # every symbol include/hsa_gpu.h and include/hsa_bwtaln.h declare
     "hsa_splice_device", "hsa_build_bwt_index_device64", "hsa_index_set_sa64", "hsa_index_set_sa64_device",
     "hsa_sa_position_batch64", "hsa_sa_position_device64", "hsa_psi_minus_batch64", "hsa_hit_positions_device64",
     "hsa_index_set_text64_device", "hsa_refine_rows_device64", "hsa_choose_hits_device64",
-    "hsa_choose_timing", "hsa_choose_launch_times",
+    "hsa_choose_timing", "hsa_choose_launch_times", "hsa_sam_lines_device64", "hsa_sam_timing",
+    "hsa_sam_launch_times",
 ]
 SP_RES_WORDS = 20  # hsa_splice_match_batch's per-read answer (include/hsa_gpu.h)
 ALN64_WORDS = 14   # hsa_aln64_t (include/hsa_gpu.h)
@@ -49,6 +50,9 @@ RF_ROW_WORDS = 8
 # hsa_choose_hits_device64: glibc's drand48 state in a process that never seeds; read types
 DRAND48_SEED0 = 0
 CHOOSE_NONE, CHOOSE_UNIQUE, CHOOSE_REPEAT = range(3)
+# hsa_sam_lines_device64: per-read status, the longest line a batch may declare
+HSA_SAM_OK, HSA_SAM_NOHIT, HSA_SAM_ROWS, HSA_SAM_REFINE, HSA_SAM_INPUT = range(5)
+HSA_SAM_MAX_LINE = 61440
 
 
 class HsaError(RuntimeError):
@@ -162,6 +166,21 @@ class ChooseBatch64(C.Structure):
                 ("d_hits", C.c_void_p), ("n_multi", C.c_uint32), ("rng_state", C.c_uint64), ("d_log_n", C.c_void_p),
                 ("d_sel", C.c_void_p), ("d_sel64", C.c_void_p), ("d_rng_out", C.c_void_p), ("d_pos_off", C.c_void_p),
                 ("d_pos", C.c_void_p), ("d_pos_hit", C.c_void_p), ("pos_cap", C.c_uint64), ("d_counters", C.c_void_p)]
+
+
+class SamBatch64(C.Structure):
+    """hsa_sam_batch64_t (include/hsa_gpu.h): the device outputs of search, choose and
+    refine and the reads' names and qualities in; the SAM text, its per-read offsets and
+    statuses out, all device pointers."""
+    _fields_ = [("d_jobs", C.c_void_p), ("n_jobs", C.c_int), ("d_codes", C.c_void_p), ("d_n_aln", C.c_void_p),
+                ("d_hit_off", C.c_void_p), ("d_hits", C.c_void_p), ("d_sel", C.c_void_p), ("d_sel64", C.c_void_p),
+                ("d_pos_off", C.c_void_p), ("d_pos", C.c_void_p), ("d_pos_hit", C.c_void_p), ("pos_cap", C.c_uint64),
+                ("d_pos_counters", C.c_void_p), ("d_rows", C.c_void_p), ("d_rpos", C.c_void_p), ("d_cigar", C.c_void_p),
+                ("d_md", C.c_void_p), ("cigar_stride", C.c_uint32), ("md_stride", C.c_uint32), ("d_names", C.c_void_p),
+                ("d_name_off", C.c_void_p), ("d_quals", C.c_void_p), ("d_qual_off", C.c_void_p),
+                ("d_chr_names", C.c_void_p), ("d_chr_off", C.c_void_p), ("n_chr", C.c_uint32), ("flag", C.c_uint32),
+                ("max_top2", C.c_int32), ("comp_read", C.c_int32), ("max_line", C.c_uint32), ("d_line_off", C.c_void_p),
+                ("d_out", C.c_void_p), ("out_cap", C.c_uint64), ("d_line_stat", C.c_void_p), ("d_counters", C.c_void_p)]
 
 
 def log_n_table() -> np.ndarray:
@@ -315,6 +334,11 @@ def lib():
         L.hsa_choose_timing.argtypes = [C.c_int]
         L.hsa_choose_timing.restype = None
         L.hsa_choose_launch_times.argtypes = [vp, f32]
+    if hasattr(L, "hsa_sam_lines_device64"):        # (older A/B builds lack the SAM lines)
+        L.hsa_sam_lines_device64.argtypes = [vp, C.POINTER(SamBatch64), vp]
+        L.hsa_sam_timing.argtypes = [C.c_int]
+        L.hsa_sam_timing.restype = None
+        L.hsa_sam_launch_times.argtypes = [vp, f32]
     if hasattr(L, "hsa_extend_batch"):
         L.hsa_extend_batch.argtypes = [vp, C.POINTER(Regime), C.c_int, vp, C.c_int, u8, i32, C.c_size_t, i32, i32,
                                        u32]
@@ -680,6 +704,25 @@ class GpuIndex:
         ms = np.zeros(len(self.CHOOSE_LAUNCHES), np.float32)
         check(lib().hsa_choose_launch_times(self._handle(), ms))
         return {k: float(v) for k, v in zip(self.CHOOSE_LAUNCHES, ms)}
+
+    def sam_lines64(self, batch: "SamBatch64", stream=None):
+        """hsa_sam_lines_device64: the SAM lines of a batch from the device outputs of
+        search_device64, choose_hits64 and refine_rows64 (batch.d_line_off, d_out,
+        d_line_stat, d_counters) on `stream` (a hipStream_t address; None: the index's own);
+        does not synchronise.  hsa_amd.sam.device_sam drives it.  Without a handle the
+        library answers itself: HSA_E_NODEV where no GPU is visible."""
+        if not hasattr(lib(), "hsa_sam_lines_device64"):
+            raise HsaError("this libhsa_gpu.so has no hsa_sam_lines_device64: rebuild it")
+        check(lib().hsa_sam_lines_device64(getattr(self, "h", None), C.byref(batch), stream))
+
+    SAM_LAUNCHES = ("len", "scan", "write")
+
+    def sam_launch_times(self) -> dict:
+        """hsa_sam_launch_times: ms per launch of this handle's last sam_lines64 call made
+        after lib().hsa_sam_timing(1); waits for it."""
+        ms = np.zeros(len(self.SAM_LAUNCHES), np.float32)
+        check(lib().hsa_sam_launch_times(self._handle(), ms))
+        return {k: float(v) for k, v in zip(self.SAM_LAUNCHES, ms)}
 
     def last_pass_ms(self):
         """(k_widths ms, k_search ms) of the last device pass on this index."""

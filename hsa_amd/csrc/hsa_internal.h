@@ -116,6 +116,10 @@ struct hsa_index {
     void *d_ch = nullptr; size_t d_ch_cap = 0;
     hipEvent_t ch_ev[HSA_CH_LAUNCHES + 1] = {};    // around its launches (hsa_choose_timing)
     bool ch_timed = false;
+    // hsa_sam_lines_device64: per-read line lengths and the scan's scratch
+    void *d_sm = nullptr; size_t d_sm_cap = 0;
+    hipEvent_t sm_ev[HSA_SAM_LAUNCHES + 1] = {};   // around its launches (hsa_sam_timing)
+    bool sm_timed = false;
     // the splice path's kernel (hsa_splice.hip): per-lane state, stacks, buffers
     void *d_sp = nullptr; size_t d_sp_cap = 0;
     uint64_t *d_ctr = nullptr;

@@ -711,6 +711,110 @@ int hsa_choose_hits_device64(hsa_index_t *ix, const hsa_choose_batch64_t *b, voi
 void hsa_choose_timing(int on);
 int hsa_choose_launch_times(hsa_index_t *ix, float *ms);
 
+/* ---- SAM lines on the 64-bit path ----
+ * bwa_print_sam1 with mate == NULL (bwtse.c:698-799) for the reads of one batch, from the
+ * outputs of search, choose and refine as they sit on the device: the finished text in
+ * device memory, in read order, ready for one copy to the host and one write().  The
+ * line of read j is what hsa_amd/sam.py: sam_line gives for it, byte for byte, and '\n':
+ *   name, flag (| 16 on strand 1, :706), chromosome name, d_rpos[2 r0 + 1], mapQ, the CIGAR
+ *   (len then "MIDNSHP=X"[op], :713), "*", "0", "0" (:720), SEQ ("ACGTN"[code]; on strand 1
+ *   the reversed read through "TGCAN", :737-742), QUAL (reversed on strand 1, or "*",
+ *   :744-749), XT:A:U|R (:762), NM|CM:i: (:763), X0:i:c1, X1:i:c2 only when c1 <= max_top2
+ *   (:766-769), XM, XO, XG (:772-774), MD:Z: (:775), and with XA rows XA:Z: and per row
+ *   chr,(+|-)pos and then its CIGAR for a gapped record (n_gapo + n_gape > 0) or
+ *   ",<n_mm + gaps>;" for an ungapped one (:781-796);
+ * tab-separated.  r0 = d_pos_off[j] is the read's chosen row, rows r0 + 1 .. r0 + n_xa
+ * (d_sel[4 j + 3]) its XA rows; a row's strand and difference counts are those of its
+ * record d_hits[d_hit_off[j] + d_pos_hit[t]]; a row's chromosome name is d_chr_names
+ * [d_chr_off[c] .. d_chr_off[c + 1]) with c the position row's chrID word (d_pos[4 t + 1]).
+ * c1, c2 and the positions print as full u64 decimals (the reference's (int) casts have no
+ * counterpart past 2^32).  The row count is min(d_pos_off[n_jobs], pos_cap,
+ * d_pos_counters[1]) (d_pos_counters may be NULL), read on the device as
+ * hsa_refine_rows_device64 reads it.
+ *
+ * Names and qualities: d_names / d_quals are bytes, d_name_off / d_qual_off n_jobs + 1
+ * offsets into them; the bytes are printed as given (the caller cuts the FASTQ comment, as
+ * the reference's reader does).  d_quals and d_qual_off both NULL: "*" for every read.
+ *
+ * Outputs:
+ *   d_line_off   n_jobs + 1: the exclusive prefix sum, in read order, of the line lengths
+ *                with the '\n'; a read without a line has length 0.  Two runs give equal
+ *                arrays.
+ *   d_out        the lines, concatenated in read order; bytes at or past out_cap are not
+ *                written and no byte past d_out + out_cap is touched.
+ *   d_line_stat  per read: HSA_SAM_OK a line; HSA_SAM_NOHIT d_sel type 0, no line (as
+ *                :922 skips it); HSA_SAM_ROWS one of its 1 + n_xa rows lies past the rows
+ *                written (pos_cap too small); HSA_SAM_REFINE the chosen row or an XA row has a
+ *                refine status other than HSA_RF_OK; HSA_SAM_INPUT an input that would
+ *                index out of bounds: a d_sel type over 2, fewer than 1 + n_xa rows between
+ *                d_pos_off[j] and [j + 1], chrID >= n_chr, d_pos_hit >= the read's n_aln, a
+ *                CIGAR op code > 8, n_cigar > cigar_stride, md_len > md_stride, a base code
+ *                > 4, a decreasing name, quality or chromosome-name offset, a quality
+ *                length other than the read's, or a line longer than max_line.  A read is
+ *                printed exactly or not at all; every index taken from a device array is
+ *                checked before it is used.  HSA_SAM_REFINE goes before HSA_SAM_INPUT.
+ *   d_counters   (>= 8 u64, zeroed by the call) [0] bytes wanted, [1] bytes written
+ *                (min(wanted, out_cap)), [2] lines, [2 + s] reads of status s (s = 1..4), [7]
+ *                the lowest read of status >= 2 (all-ones: none).  [0] > [1]: run again
+ *                with more room (the hit_cap convention).
+ * max_line bounds the batch's longest line (with its '\n'; 1..HSA_SAM_MAX_LINE, HSA_E_ARG otherwise):
+ * it sizes the tile of the writing kernel (below), so the caller states it; hsa_amd/sam.py:
+ * line_bound computes one from the strings' lengths and the strides.
+ *
+ * A sub-range [s, e) of a batch is served as the choice's: d_jobs + s, d_n_aln + s,
+ * d_hit_off + s, d_sel + 4 s, d_sel64 + 4 s, d_name_off + s, d_qual_off + s, n_jobs = e - s;
+ * d_codes, d_hits, the string bytes and the row arrays (which start at 0 for every call of
+ * the choice) as they are.
+ *
+ * Three launches on `stream` (NULL = the library's): k_sam_len (one lane per read: status
+ * and exact length), the exclusive scan, k_sam_write (one wavefront per tile of consecutive
+ * reads: the tile's contiguous range is assembled in LDS and leaves in aligned 16-byte
+ * stores, its ragged ends as byte stores).  No atomics place anything.  The call does not
+ * synchronise; scratch grows on the handle (hsa_index_release_scratch).  Null pointers and
+ * inconsistent sizes: HSA_E_ARG.
+ *
+ * Not built: spliced reads (N ops, XT:A:S), trimmed reads (bwa_correct_trimmed, the XC
+ * tag, the reference's reversal of only `len` quality bytes of a full_len read), RG and BC
+ * tags, paired reads, the @SQ header lines, a 32-bit-record (bwt_aln1_t) variant.  The
+ * drop-in's host SAM stage stays as it is. */
+#define HSA_SAM_OK     0u
+#define HSA_SAM_NOHIT  1u
+#define HSA_SAM_ROWS   2u
+#define HSA_SAM_REFINE 3u
+#define HSA_SAM_INPUT  4u
+#define HSA_SAM_MAX_LINE 61440u
+typedef struct {
+    const hsa_job_t *d_jobs; int n_jobs;
+    const uint8_t *d_codes;
+    const int32_t *d_n_aln; const uint64_t *d_hit_off; const uint32_t *d_hits;   /* hsa_aln64_t */
+    const uint32_t *d_sel; const uint64_t *d_sel64;          /* the choice's */
+    const uint64_t *d_pos_off; const uint64_t *d_pos; const uint32_t *d_pos_hit;
+    uint64_t pos_cap;
+    const uint64_t *d_pos_counters;  /* the choice's counters, or NULL */
+    const uint32_t *d_rows; const uint64_t *d_rpos;          /* the refinement's */
+    const uint32_t *d_cigar; const uint8_t *d_md;
+    uint32_t cigar_stride, md_stride;
+    const uint8_t *d_names; const uint64_t *d_name_off;      /* n_jobs + 1 */
+    const uint8_t *d_quals; const uint64_t *d_qual_off;      /* n_jobs + 1, or both NULL */
+    const uint8_t *d_chr_names; const uint64_t *d_chr_off;   /* n_chr + 1 */
+    uint32_t n_chr;
+    uint32_t flag;                   /* the reads' extra_flag */
+    int32_t max_top2;                /* gap_opt_t.max_top2 */
+    int32_t comp_read;               /* BWA_MODE_COMPREAD: NM, else CM */
+    uint32_t max_line;               /* the longest line the batch can have, '\n' included */
+    uint64_t *d_line_off;            /* n_jobs + 1 */
+    uint8_t *d_out; uint64_t out_cap;
+    uint32_t *d_line_stat;           /* n_jobs */
+    uint64_t *d_counters;            /* >= 8 u64 */
+} hsa_sam_batch64_t;
+int hsa_sam_lines_device64(hsa_index_t *ix, const hsa_sam_batch64_t *b, void *stream);
+/* Probes, as hsa_choose_timing / hsa_choose_launch_times: the HSA_SAM_LAUNCHES times in ms of
+ * the handle's last timed call: k_sam_len (with the counters' memsets), the scan,
+ * k_sam_write. */
+#define HSA_SAM_LAUNCHES 3
+void hsa_sam_timing(int on);
+int hsa_sam_launch_times(hsa_index_t *ix, float *ms);
+
 #ifdef __cplusplus
 }
 #endif
