@@ -19,7 +19,7 @@
 #include "hsa_trie.h"
 
 static thread_local char g_err[1024] = "";
-int g_waves_per_cu = 16;
+int g_waves_per_cu = 32;
 int g_pool_entries = 0;      // 0: 8192 per lane, 32768 when gap opens are allowed
 // k_search: when a wave runs the strand-end / next-read paths of its waiting lanes:
 // at most HSA_BATCH_K waiting lanes, or HSA_BATCH_IDLE lane-iterations of waiting

@@ -310,6 +310,7 @@ static long search_batch_impl(hsa_index_t *ix, const hsa_regime_t *regimes, int 
     RegimePlan R = regime_plan(regimes, n_regimes);
     R.nb = H.nb;
     R.nib_ok = R.nib_ok && !mh;
+    R.snib_ok = R.snib_ok && !mh;            // caller widths (k_widths_import): byte rows
     for (int j = 0; j < n_jobs && R.nib_ok; ++j) R.nib_ok = jobs[j].max_diff <= 6;
     if ((rc = plan_launch(ix, n_jobs, max_len, max_seed, R, PASS_MAIN, P))) return rc;
     HSA_HIP(hipEventRecord(ix->ev0, st));

@@ -82,7 +82,7 @@ struct SearchArgs {
     uint32_t *hbuf;
     uint32_t pcap, hcap, nb;
     uint32_t off_heads, off_wb, off_ws;   // LDS byte offsets
-    uint32_t nib_wb, nib_ws;              // 4-bit layout: LDS words per lane of the read / seed row
+    uint32_t lds_wb, lds_ws;              // LDS words per lane of the read / seed row (every format)
     uint32_t mm_buckets;           // 1: the bucket of every score is its n_mm (no gap opens, s_mm > 0)
     // device-side overflow re-run: the main pass appends reads that exceeded their
     // lane's capacity to ovf_list (count in ctr[ovf_ctr]); the re-run pass takes its read
@@ -359,6 +359,14 @@ template <> struct WFmt<WNib> {
     static constexpr uint32_t BIDB = 3u, BIDM = 7u, EQ = 8u, EB = 4u, EPW = 8u;
 };
 
+// The mixed format (SN, "seed nibbles") of 8-bit rows: the read row stays 8-bit and the seed
+// row, which carries no base code and whose bids are only compared with max_seed_diff - ...
+// - 1 (bwtgap.c:259-263), is 4-bit, exact while max_seed_diff <= 6.  k_widths writes it to
+// HBM already packed (width_step with WFmt<WNib>'s constants), so k_search still copies both
+// rows with the one-wait LDS-DMA, and the read row's LDS copy drops element len: a 100 bp
+// read with a 32-base seed takes 25 + 4 LDS words per lane instead of 26 + 9.
+template <typename WT, bool SN> using SeedFmt = WFmt<typename std::conditional<SN, WNib, WT>::type>;
+
 // four 8-bit elements (WFmt<uint8_t>) -> four 4-bit ones in the low 16 bits
 __device__ __forceinline__ uint32_t nib4(uint32_t x)
 {
@@ -469,7 +477,7 @@ __device__ __forceinline__ uint8_t cost_key(const SearchArgs &a, const WRow &w)
     return (uint8_t)(b << 4 | (w.tail < 16u ? 2u : w.tail < 48u ? 1u : 0u));
 }
 
-template <typename WT, typename IT>
+template <typename WT, typename IT, bool SN = false>
 __device__ __forceinline__ WRow width_row(const SearchArgs &a, uint32_t R, uint32_t strand, const hsa_job_t &J)
 {
     using F = WFmt<WT>;
@@ -513,7 +521,8 @@ __device__ __forceinline__ WRow width_row(const SearchArgs &a, uint32_t R, uint3
         width_step<WT, IT>(a, f, t, len, cf, t < len ? F::code_bits(cf) : 0u, brow, wrow, st_q, st_b, st_t);
         if (has_seed && t <= slen) {
             const uint32_t cs = t < slen ? base(s0 + t, 1) : 4u;
-            width_step<WT, IT>(a, sd, t, slen, cs, 0u, srow, nullptr, st_q, st_b, st_t);
+            width_step<typename std::conditional<SN, WNib, WT>::type, IT>(a, sd, t, slen, cs, 0u, srow, nullptr, st_q,
+                                                                          st_b, st_t);
         }
     }
     return WRow{st_q, st_b, st_t, f.bid, len - f.lr};
@@ -532,7 +541,7 @@ __device__ __forceinline__ void wave_add(unsigned long long *c, unsigned long lo
 // One lane per row (rows in order): row = list position * 2 + strand.  The forward
 // strand's rows are computed speculatively and count as the reference's work only
 // when k_search searches that strand (ctr[CTR_FWD_Q_ALL]: all of them).
-template <typename WT, typename IT = uint32_t>
+template <typename WT, typename IT = uint32_t, bool SN = false>
 __global__ void __launch_bounds__(BLOCK) k_widths(SearchArgs a)
 {
     const uint32_t R = blockIdx.x * BLOCK + threadIdx.x;     // row = list position * 2 + strand
@@ -541,7 +550,7 @@ __global__ void __launch_bounds__(BLOCK) k_widths(SearchArgs a)
     WRow w{0, 0, 0, 0};
     if (R < 2u * n_jobs) {
         const hsa_job_t J = a.jobs[a.job_list ? a.job_list[q] : (int)q];
-        w = width_row<WT, IT>(a, R, strand, J);
+        w = width_row<WT, IT, SN>(a, R, strand, J);
         if (!strand) a.wq[q] = w.q;
         if (a.wkey) a.wkey[R] = cost_key(a, w);
     }
@@ -561,7 +570,7 @@ __global__ void __launch_bounds__(BLOCK) k_widths(SearchArgs a)
 // mode 3: the forward rows of list2 (the speculative count, as k_widths').
 // mode 2 (the forward pass): the forward rows of the reads k_search listed, the
 //   reference's work.
-template <typename WT, typename IT = uint32_t>
+template <typename WT, typename IT = uint32_t, bool SN = false>
 __global__ void __launch_bounds__(BLOCK) k_widths_reads(SearchArgs a, uint32_t mode, int32_t *list2,
                                                         unsigned long long *n2)
 {
@@ -575,7 +584,7 @@ __global__ void __launch_bounds__(BLOCK) k_widths_reads(SearchArgs a, uint32_t m
         // mode 1: the rc plane (row q); mode 3: the forward plane after it (row n_al + p);
         // mode 2 (forward pass, no plane map): row 2 p
         const uint32_t R = mode == 1 ? q : mode == 3 ? (uint32_t)(((uint32_t)a.n_jobs + 63u) & ~63u) + p : 2u * q;
-        w = width_row<WT, IT>(a, R, mode == 1 ? 1u : 0u, J);
+        w = width_row<WT, IT, SN>(a, R, mode == 1 ? 1u : 0u, J);
         if (mode == 3) a.rmap[q] = (int32_t)R;
         const uint8_t key = cost_key(a, w);
         if (mode == 1) {
@@ -763,15 +772,18 @@ static __global__ void __launch_bounds__(BLOCK) k_split_finalize(SearchArgs a)
     }
 }
 
-// NT = lanes per workgroup: 256, or 64 when per-lane LDS (many buckets, long reads)
-// would leave fewer than 16 waves per CU in 256-lane workgroups (plan_launch)
+// NT = lanes per workgroup: 256, or 64 when that puts more waves on the CU (per-lane
+// LDS: many buckets, long reads; the mixed format's 19 waves) (plan_launch)
 // HUGE: the last capacity pass (reads that overflowed the big pass): 32-bit pool
 // links and popped slots reused through a free list, so a lane's pool holds any
 // stack the reference can build (n_entries <= max_entries + 9, bwtgap.c:150-151).
-template <int MW, bool GAPS, typename WT, int NT, bool HUGE = false, typename IT = uint32_t>
+// SN: the mixed format, 4-bit seed row beside the 8-bit read row (SeedFmt)
+template <int MW, bool GAPS, typename WT, int NT, bool HUGE = false, typename IT = uint32_t, bool SN = false>
 __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
 {
     using F = WFmt<WT>;
+    using FS = SeedFmt<WT, SN>;                      // the seed row's elements
+    static_assert(!SN || (std::is_same<WT, uint8_t>::value && !HUGE), "mixed format: 8-bit rows, not the HUGE pass");
     using E = Ent<IT>;
     using CT = typename std::conditional<sizeof(IT) == 8, int64_t, int>::type;   // best_cnt (int in bwtgap.c:127)
     constexpr uint32_t HW = HitW<IT>::STAGE, OW = HitW<IT>::OUT;
@@ -886,7 +898,7 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
         else return WB(p);
     };
     auto wsg = [&](int p) -> uint32_t {
-        if constexpr (F::NIB) return (s_ns[((uint32_t)p >> 3) * NT + tid] >> (((uint32_t)p & 7u) * 4u)) & 15u;
+        if constexpr (FS::NIB) return (s_ns[((uint32_t)p >> 3) * NT + tid] >> (((uint32_t)p & 7u) * 4u)) & 15u;
         else return WS(p);
     };
     auto wbs = [&](int p, uint32_t v) {
@@ -994,17 +1006,20 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
                         if (j + u < nn) dst[(j + u) * NT + tid] = nib4(w[2u * u]) | nib4(w[2u * u + 1u]) << 16;
                 }
             };
-            pack(src, nwb, s_nb, r->nib_wb);
+            pack(src, nwb, s_nb, r->lds_wb);
             if (C_SEED(ctl) && !C_ALIAS(ctl))
-                pack(reinterpret_cast<const uint32_t *>(r->ws) + row_base(r->rs / 4), r->rs / 4, s_ns, r->nib_ws);
+                pack(reinterpret_cast<const uint32_t *>(r->ws) + row_base(r->rs / 4), r->rs / 4, s_ns, r->lds_ws);
         } else {
+        // the words the lane's LDS columns hold: the whole HBM row, or in the mixed format
+        // the words of elements 0 .. len - 1 (the HBM rows' last word may hold element len alone)
         uint32_t *const db = reinterpret_cast<uint32_t *>(s_wb) + (tid & ~63u);
-        for (uint32_t q = 0; q < nwb; ++q)
+        const uint32_t lwb = SN ? r->lds_wb : nwb;
+        for (uint32_t q = 0; q < lwb; ++q)
             __builtin_amdgcn_global_load_lds(src + q * 64, db + q * NT, 4, 0, 0);
         if (C_SEED(ctl) && !C_ALIAS(ctl)) {
             const uint32_t *ss = reinterpret_cast<const uint32_t *>(r->ws) + row_base(r->rs / 4);
             uint32_t *const ds = reinterpret_cast<uint32_t *>(s_ws) + (tid & ~63u);
-            const uint32_t nws = r->rs / 4;
+            const uint32_t nws = SN ? r->lds_ws : r->rs / 4;
             for (uint32_t q = 0; q < nws; ++q)
                 __builtin_amdgcn_global_load_lds(ss + q * 64, ds + q * NT, 4, 0, 0);
         }
@@ -1706,11 +1721,13 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
                     int ems = RG(max_seed_diff) - (emm + ego);
                     if (R_MODE & MODE_GAPE) ems -= ege;
                     // width_seed aliased to width_back (bwtgap.c:809): the same LDS row
-                    const uint32_t s1 = C_ALIAS(ctl) ? wbg(ii - 1) : wsg(ii - 1);
-                    const uint32_t s0 = C_ALIAS(ctl) ? wbg(ii) : wsg(ii);
-                    const int c1 = (int)(s1 & F::BIDM), c0 = (int)(s0 & F::BIDM);
+                    // (never in the mixed format: caller-width passes keep byte rows)
+                    const bool alias = !SN && C_ALIAS(ctl);
+                    const uint32_t s1 = alias ? wbg(ii - 1) : wsg(ii - 1);
+                    const uint32_t s0 = alias ? wbg(ii) : wsg(ii);
+                    const int c1 = (int)(s1 & FS::BIDM), c0 = (int)(s0 & FS::BIDM);
                     if (c1 > ems - 1) allow_diff = 0;
-                    else if (c1 == ems - 1 && c0 == ems - 1 && (s1 & F::EQ)) allow_M = 0;
+                    else if (c1 == ems - 1 && c0 == ems - 1 && (s1 & FS::EQ)) allow_M = 0;
                 }
             }
             // The pushes of bwtgap.c:267-325 as a candidate mask in push order:

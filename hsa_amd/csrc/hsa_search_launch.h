@@ -3,6 +3,9 @@
 // a pass's launch plan, one pass (launch_pass), the MAIN -> BIG -> HUGE capacity cascade
 // (run_capacity_passes), the k_search_any passes, hsa_search_device's implementation.
 // Included by hsa_search.hip (32-bit API) and hsa_search64.hip (64-bit API).
+#include <map>
+#include <mutex>
+
 #include "hsa_search_kernels.h"
 
 // ---------------------------------------------------------------- host helpers (both TUs)
@@ -79,21 +82,24 @@ static bool mm_buckets(const hsa_regime_t *rg, int n, const uint8_t *bmap)
 // What the regimes of a search decide for its passes: gap opens possible; 16-bit pruning
 // elements when a bid may be compared with a bound above 14 (WFmt); 4-bit ones exact while
 // every such bound is <= 6 (WFmt<WNib>; a job's max_diff never exceeds its regime's); the
-// HUGE pass's bound on live stack entries.  nb, the stack buckets, is stage_regimes'.
+// mixed format (4-bit seed row, SeedFmt) exact while max_seed_diff <= 6, for rows k_widths
+// writes (caller-width passes clear snib_ok); the HUGE pass's bound on live stack entries.
+// nb, the stack buckets, is stage_regimes'.
 struct RegimePlan {
     int nb;
-    bool gaps, wide, nib_ok;
+    bool gaps, wide, nib_ok, snib_ok;
     int max_entries;
 };
 
 static RegimePlan regime_plan(const hsa_regime_t *rg, int n)
 {
-    RegimePlan C{.nb = 0, .gaps = false, .wide = false, .nib_ok = true, .max_entries = 0};
+    RegimePlan C{.nb = 0, .gaps = false, .wide = false, .nib_ok = true, .snib_ok = true, .max_entries = 0};
     for (int r = 0; r < n; ++r) {
         const int bound = rg[r].max_diff > rg[r].max_seed_diff ? rg[r].max_diff : rg[r].max_seed_diff;
         C.gaps |= rg[r].max_gapo > 0;
         C.wide |= bound > 14;
         C.nib_ok &= bound <= 6;
+        C.snib_ok &= rg[r].max_seed_diff <= 6;
         C.max_entries = rg[r].max_entries > C.max_entries ? rg[r].max_entries : C.max_entries;
     }
     return C;
@@ -105,8 +111,9 @@ struct LaunchPlan {
     uint32_t pcap, hcap, nb;
     bool gaps, wide;                 // gap opens possible; 16-bit pruning elements (WFmt)
     bool nib;                        // 4-bit pruning elements in LDS (WFmt<WNib>)
+    bool snib;                       // 8-bit read row, 4-bit seed row, in HBM and LDS (SeedFmt)
     uint32_t off_heads, off_wb, off_ws;
-    uint32_t nib_wb, nib_ws;         // 4-bit rows: LDS words per lane (SearchArgs)
+    uint32_t lds_wb, lds_ws;         // LDS words per lane of the read / seed row (SearchArgs)
     size_t lds;
     bool huge;                       // PASS_HUGE: 32-bit links, reused slots
     uint32_t ntab;                   // score table entries per regime in LDS
@@ -119,9 +126,59 @@ struct LaunchPlan {
 // BIG: reused slots up to max_entries + 16 live entries, 262 144 hits).
 enum { PASS_MAIN = 0, PASS_BIG = 1, PASS_HUGE = 2 };
 
-static int plan_launch(hsa_index *ix, int n_jobs, int max_len, int max_seed, const RegimePlan &R, int mode,
-                       LaunchPlan &P, uint32_t ent_bytes = 16)
+// The k_search instantiation a plan runs.
+using SearchFn = void (*)(SearchArgs);
+
+template <typename WT, int NT, typename IT, bool SN>
+static SearchFn search_kernel_nt(const LaunchPlan &P)
 {
+    if (P.nb <= 32) return P.gaps ? k_search<0, true, WT, NT, false, IT, SN> : k_search<0, false, WT, NT, false, IT, SN>;
+    if (P.nb <= 64) return P.gaps ? k_search<1, true, WT, NT, false, IT, SN> : k_search<1, false, WT, NT, false, IT, SN>;
+    return P.gaps ? k_search<2, true, WT, NT, false, IT, SN> : k_search<2, false, WT, NT, false, IT, SN>;
+}
+
+template <typename IT>
+static SearchFn search_kernel(const LaunchPlan &P)
+{
+    if (P.nib)                                       // never a HUGE pass (plan_launch)
+        return P.nt == 64 ? search_kernel_nt<WNib, 64, IT, false>(P) : search_kernel_nt<WNib, 256, IT, false>(P);
+    if (P.snib)                                      // nor this: 8-bit rows only
+        return P.nt == 64 ? search_kernel_nt<uint8_t, 64, IT, true>(P) : search_kernel_nt<uint8_t, 256, IT, true>(P);
+    if (P.huge) {
+        if (P.wide) return P.gaps ? k_search<2, true, uint16_t, 64, true, IT> : k_search<2, false, uint16_t, 64, true, IT>;
+        return P.gaps ? k_search<2, true, uint8_t, 64, true, IT> : k_search<2, false, uint8_t, 64, true, IT>;
+    }
+    if (P.wide) return P.nt == 64 ? search_kernel_nt<uint16_t, 64, IT, false>(P) : search_kernel_nt<uint16_t, 256, IT, false>(P);
+    return P.nt == 64 ? search_kernel_nt<uint8_t, 64, IT, false>(P) : search_kernel_nt<uint8_t, 256, IT, false>(P);
+}
+
+// Waves per SIMD a kernel's registers allow: gfx950 gives a wave its VGPRs in granules of 8
+// out of 512 per lane, at most 8 waves.  Asked of the runtime once per instantiation; 4,
+// what k_search's launch bound guarantees, where it does not say.
+static int kernel_waves_simd(SearchFn f)
+{
+    static std::mutex mu;
+    static std::map<SearchFn, int> known;
+    std::lock_guard<std::mutex> lock(mu);
+    const auto it = known.find(f);
+    if (it != known.end()) return it->second;
+    int w = HSA_WAVES_SIMD;
+    hipFuncAttributes at{};
+    if (hipFuncGetAttributes(&at, reinterpret_cast<const void *>(f)) == hipSuccess && at.numRegs > 0) {
+        w = 512 / ((at.numRegs + 7) / 8 * 8);
+        w = w > 8 ? 8 : w < 1 ? 1 : w;
+    } else {
+        (void)hipGetLastError();
+    }
+    known[f] = w;
+    return w;
+}
+
+template <typename IT = uint32_t>
+static int plan_launch(hsa_index *ix, int n_jobs, int max_len, int max_seed, const RegimePlan &R, int mode,
+                       LaunchPlan &P)
+{
+    constexpr uint32_t ent_bytes = 4u * sizeof(IT);  // pool entry bytes
     const int nb = R.nb, max_entries = R.max_entries;
     const bool gaps = R.gaps, wide = R.wide, nib_ok = R.nib_ok;
     const bool big = mode == PASS_BIG;
@@ -132,11 +189,19 @@ static int plan_launch(hsa_index *ix, int n_jobs, int max_len, int max_seed, con
     P.wide = wide;
     const uint32_t esz = wide ? 2u : 1u;
     P.nib = false;
-    // Resident workgroups per CU, from gfx950's own limits: 160 KiB of LDS per CU, at
-    // most 16 waves (__launch_bounds__(NT, 4) caps VGPRs at 4 waves per SIMD).  The
-    // per-lane LDS (bucket heads, pruning rows) decides between 256-lane workgroups
-    // and 64-lane ones, which pack the CU's LDS more finely: -n 4 -o 1 has 39 buckets
-    // and ~220 B per lane, i.e. 2 workgroups of 256 (8 waves) but 11 of 64 (11 waves).
+    P.snib = false;
+    // Resident workgroups per CU, from gfx950's own limits: 160 KiB of LDS per CU, and 4
+    // waves per SIMD, which __launch_bounds__(NT, 4) guarantees -- or, in the mixed
+    // format, what the registers of the instantiation the plan runs allow
+    // (kernel_waves_simd: the bound is a ceiling of 128 VGPRs, not the occupancy; config
+    // 2's 64-lane kernel takes 95, i.e. 5 waves per SIMD, 20 per CU).  Only there: with
+    // byte rows the same cap put config 4's ungapped splice-seed searches on 20 waves
+    // per CU and its step went from 702 to 665 k reads/s (profiles/seednib_ab.log).
+    // The per-lane LDS (bucket heads, pruning rows) decides between 256-lane
+    // workgroups and 64-lane ones, which pack the CU's LDS more finely: -n 4 -o 1 has 39
+    // buckets and ~220 B per lane, i.e. 2 workgroups of 256 (8 waves) but 11 of 64 (11
+    // waves); -n 4 -o 0 on 100 bp reads in the mixed format has 8 432 B per 64 lanes,
+    // 19 workgroups = 19 waves, where 256-lane workgroups stop at 4 = 16 waves.
     // (hipOccupancyMaxActiveBlocksPerMultiprocessor is not used: depending on which
     // HIP runtime the process loaded first it assumed 64 KiB of LDS and halved the
     // grid -- measured 512 instead of 1024 workgroups, 1.5x slower.)
@@ -148,24 +213,25 @@ static int plan_launch(hsa_index *ix, int n_jobs, int max_len, int max_seed, con
         // k_search reads elements 0 .. len - 1 of a row (pops of position i read i - 1,
         // expansions i - 1 and i < len; seed rows ii - 1 and ii < seed_len): the 4-bit
         // rows keep just those, which takes config 5's 64-lane workgroups from 15 to 16
-        // per CU; the 8-bit rows keep element len too (the LDS-DMA copies whole words)
-        P.nib_wb = ((uint32_t)max_len + 7u) / 8u;
-        P.nib_ws = ((uint32_t)max_seed + 7u) / 8u;
-        const uint32_t wbw = P.nib ? P.nib_wb : (uint32_t)max_len / epw + 1u;
-        const uint32_t wsw = P.nib ? P.nib_ws : (uint32_t)max_seed / epw + 1u;
-        P.off_ws = P.off_wb + wbw * nt * 4u;
-        P.lds = ((size_t)P.off_ws + (size_t)wsw * nt * 4u + 15) / 16 * 16;
+        // per CU, and so does the mixed format (its read row: ceil(len / 4) words, its
+        // seed row ceil(seed_len / 8)); the plain 8-bit rows keep element len too (the
+        // LDS-DMA copies the HBM row's whole capacity)
+        P.lds_wb = P.nib ? ((uint32_t)max_len + 7u) / 8u : P.snib ? ((uint32_t)max_len + 3u) / 4u : (uint32_t)max_len / epw + 1u;
+        P.lds_ws = P.nib || P.snib ? ((uint32_t)max_seed + 7u) / 8u : (uint32_t)max_seed / epw + 1u;
+        P.off_ws = P.off_wb + P.lds_wb * nt * 4u;
+        P.lds = ((size_t)P.off_ws + (size_t)P.lds_ws * nt * 4u + 15) / 16 * 16;
         int per_cu = (int)((160u * 1024u) / P.lds);
-        const int cap = 4 * HSA_WAVES_SIMD / (int)(nt / 64);  // 16 waves per CU
+        const int simd = P.snib ? kernel_waves_simd(search_kernel<IT>(P)) : HSA_WAVES_SIMD;
+        const int cap = 4 * simd / (int)(nt / 64);
         const int want = g_waves_per_cu / (int)(nt / 64);
         if (per_cu > cap) per_cu = cap;
         if (per_cu > want) per_cu = want > 0 ? want : 1;
         return per_cu;
     };
     static const int force256 = getenv("HSA_WG256") != nullptr;   // A/B runs only
-    auto best = [&]() {
+    auto best = [&]() {                              // the workgroup size with more waves per CU
         int per_cu = layout(P.huge ? 64 : 256);
-        if (per_cu < 4 && !force256 && !P.huge) {
+        if (!force256 && !P.huge) {
             const int p64 = layout(64);
             if (p64 > per_cu * 4) per_cu = p64;
             else per_cu = layout(256);
@@ -173,17 +239,36 @@ static int plan_launch(hsa_index *ix, int n_jobs, int max_len, int max_seed, con
         return per_cu;
     };
     int per_cu = best();
+    const char *wf = getenv("HSA_WFMT");
+    const bool force_nib = wf && !strcmp(wf, "nib"), no_nib = wf && !strcmp(wf, "byte");
+    const bool force_snib = wf && !strcmp(wf, "seednib");
+    // The mixed format (4-bit seed row, the read row without element len) where it puts
+    // more waves on the CU, in ungapped searches: config 2 runs 19 workgroups of 64 lanes
+    // per CU instead of 4 of 256.  A launch on its own takes as long as before (the gain
+    // of waves ends at 16: 12 / 14 / 16 / 19 waves 16.4 / 15.7 / 14.6 / 14.8 ms); steps
+    // that overlap on several handles, as the bench's do, run 3 % faster (59.1-59.8 ->
+    // 60.4-61.2 M reads/s, the same library with HSA_WFMT=byte and without,
+    // profiles/seednib_ab.log).  Gapped searches keep byte rows unless forced.
+    // HSA_WFMT=seednib forces it where it is exact, =byte forbids it.
+    if (R.snib_ok && !wide && !P.huge && !no_nib && max_seed > 0 && (force_snib || !gaps)) {
+        const int waves8 = per_cu * (int)(P.nt / 64);
+        const LaunchPlan keep = P;
+        P.snib = true;
+        const int per_sn = best();
+        if (!force_snib && per_sn * (int)(P.nt / 64) <= waves8) { P = keep; }
+        else per_cu = per_sn;
+    }
     // long reads: 4-bit elements when the 8-bit rows leave the CU short of 16 waves, in
     // ungapped searches, which are latency-bound: config 5's k_search 45.6 -> 38.4 ms.
     // Gapped ones are issue-bound and lose more to the unpacking and the base loads
     // than they gain in waves (config 4: 1 988 -> 2 147 ms; config 3: equal).
     // HSA_WFMT=nib forces them where exact, =byte keeps 8-bit (tests and A/B runs).
-    const char *wf = getenv("HSA_WFMT");
-    const bool force_nib = wf && !strcmp(wf, "nib"), no_nib = wf && !strcmp(wf, "byte");
-    if (nib_ok && !wide && !P.huge && !no_nib && (force_nib || (!gaps && per_cu * (int)(P.nt / 64) < 16))) {
+    if (nib_ok && !wide && !P.huge && !no_nib && !force_snib &&
+        (force_nib || (!gaps && per_cu * (int)(P.nt / 64) < 16))) {
         const int waves8 = per_cu * (int)(P.nt / 64);
         const LaunchPlan keep = P;
         P.nib = true;
+        P.snib = false;
         const int per_nib = best();
         if (!force_nib && per_nib * (int)(P.nt / 64) <= waves8) { P = keep; }
         else per_cu = per_nib;
@@ -215,7 +300,7 @@ static int plan_launch(hsa_index *ix, int n_jobs, int max_len, int max_seed, con
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_search<1, true, uint8_t, 256>, 256, P.lds);
         fprintf(stderr, "[hsa] launch: %d CUs x %d workgroups of %u lanes (runtime occupancy query says %d), "
                 "LDS %zu B, %zu workgroups, %d buckets%s\n", ix->n_cu, per_cu, P.nt, occ, P.lds, blocks, nb,
-                P.nib ? ", 4-bit rows" : "");
+                P.nib ? ", 4-bit rows" : P.snib ? ", 4-bit seed row" : "");
     }
     // pool slots are not reused within a search: gapped searches push many more.  A
     // deeper main-pass pool keeps the long gapped searches inside the main pass, where
@@ -253,40 +338,10 @@ static int plan_launch(hsa_index *ix, int n_jobs, int max_len, int max_seed, con
     return 0;
 }
 
-template <typename WT, int NT, typename IT>
-static void launch_search_nt(const LaunchPlan &P, const SearchArgs &A, hipStream_t st)
-{
-    const dim3 g((unsigned)P.blocks), b(NT);
-    if (P.nb <= 32) {
-        if (P.gaps) hipLaunchKernelGGL((k_search<0, true, WT, NT, false, IT>), g, b, P.lds, st, A);
-        else hipLaunchKernelGGL((k_search<0, false, WT, NT, false, IT>), g, b, P.lds, st, A);
-    } else if (P.nb <= 64) {
-        if (P.gaps) hipLaunchKernelGGL((k_search<1, true, WT, NT, false, IT>), g, b, P.lds, st, A);
-        else hipLaunchKernelGGL((k_search<1, false, WT, NT, false, IT>), g, b, P.lds, st, A);
-    } else {
-        if (P.gaps) hipLaunchKernelGGL((k_search<2, true, WT, NT, false, IT>), g, b, P.lds, st, A);
-        else hipLaunchKernelGGL((k_search<2, false, WT, NT, false, IT>), g, b, P.lds, st, A);
-    }
-}
-
-template <typename WT, typename IT>
+template <typename IT>
 static void launch_search(const LaunchPlan &P, const SearchArgs &A, hipStream_t st)
 {
-    if constexpr (!std::is_same<WT, WNib>::value) {
-        if (P.nib) {                                 // never a HUGE pass (plan_launch)
-            if (P.nt == 64) launch_search_nt<WNib, 64, IT>(P, A, st);
-            else launch_search_nt<WNib, 256, IT>(P, A, st);
-            return;
-        }
-    }
-    if (P.huge) {
-        const dim3 g((unsigned)P.blocks), b(64);
-        if (P.gaps) hipLaunchKernelGGL((k_search<2, true, WT, 64, true, IT>), g, b, P.lds, st, A);
-        else hipLaunchKernelGGL((k_search<2, false, WT, 64, true, IT>), g, b, P.lds, st, A);
-        return;
-    }
-    if (P.nt == 64) launch_search_nt<WT, 64, IT>(P, A, st);
-    else launch_search_nt<WT, 256, IT>(P, A, st);
+    hipLaunchKernelGGL(search_kernel<IT>(P), dim3((unsigned)P.blocks), dim3(P.nt), P.lds, st, A);
 }
 
 // The levels of the index's root width trie that kernels of this interval width use (0:
@@ -338,7 +393,9 @@ static int pass_args(hsa_index *ix, const LaunchPlan &P, SearchScratch &S, const
     constexpr size_t WGB = sizeof(IT);       // bytes per full w value (wg rows)
     const bool mg = io.mg.d_mg != nullptr;
     const uint32_t esz = P.wide ? 2u : 1u;
-    const uint32_t rb = (((uint32_t)io.max_len + 1u) * esz + 3u) & ~3u, rs = (((uint32_t)io.max_seed + 1u) * esz + 3u) & ~3u;
+    // HBM row capacities: elements 0 .. len (seed_len) at esz bytes each; the mixed format's seed row at 4 bits
+    const uint32_t rb = (((uint32_t)io.max_len + 1u) * esz + 3u) & ~3u;
+    const uint32_t rs = P.snib ? ((uint32_t)io.max_seed / 8u + 1u) * 4u : (((uint32_t)io.max_seed + 1u) * esz + 3u) & ~3u;
     const uint32_t rg = (uint32_t)io.max_len + 1u;
     const size_t rows = ((size_t)io.n + 63) / 64 * 64 * 2;     // two 64-row-aligned planes (lazy widths)
     const size_t row_bytes = rb + rs + WGB * (size_t)rg + (mg ? 4 * (size_t)rg : 0);   // + full bids (caller widths)
@@ -362,7 +419,7 @@ static int pass_args(hsa_index *ix, const LaunchPlan &P, SearchScratch &S, const
     A.pool = S.pool; A.nxt = S.nxt; A.hbuf = S.hbuf;
     A.pcap = P.pcap; A.hcap = P.hcap;        // the planned capacities (the scratch may be larger)
     A.nb = P.nb; A.off_heads = P.off_heads; A.off_wb = P.off_wb; A.off_ws = P.off_ws;
-    A.nib_wb = P.nib_wb; A.nib_ws = P.nib_ws;
+    A.lds_wb = P.lds_wb; A.lds_ws = P.lds_ws;
     A.mm_buckets = ix->staged_mmb ? 1u : 0u;
     A.ntab = P.ntab;
     A.batch_k = (uint32_t)g_batch_k;
@@ -515,8 +572,7 @@ static int launch_pass(hsa_index *ix, const LaunchPlan &P0, SearchScratch &S, co
             else hipLaunchKernelGGL(k_widths_import<uint8_t>, dim3(nb ? nb : 1), dim3(BLOCK), 0, st, A);
             HSA_HIP(hipGetLastError());
             if (ix->ev_split) HSA_HIP(hipEventRecord(ix->ev_split, st));
-            if (P.wide) launch_search<uint16_t, uint32_t>(P, A, st);
-            else launch_search<uint8_t, uint32_t>(P, A, st);
+            launch_search<uint32_t>(P, A, st);
             HSA_HIP(hipGetLastError());
             hipLaunchKernelGGL(k_widths_export, dim3(nb ? nb : 1), dim3(BLOCK), 0, st, A);
             HSA_HIP(hipGetLastError());
@@ -580,6 +636,9 @@ static int launch_pass(hsa_index *ix, const LaunchPlan &P0, SearchScratch &S, co
         if (P.wide) {
             hipLaunchKernelGGL((k_widths_reads<uint16_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, A, 1u, d_list2, d_n2);
             hipLaunchKernelGGL((k_widths_reads<uint16_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, A, 3u, d_list2, d_n2);
+        } else if (P.snib) {
+            hipLaunchKernelGGL((k_widths_reads<uint8_t, IT, true>), dim3(rblocks), dim3(BLOCK), 0, st, A, 1u, d_list2, d_n2);
+            hipLaunchKernelGGL((k_widths_reads<uint8_t, IT, true>), dim3(rblocks), dim3(BLOCK), 0, st, A, 3u, d_list2, d_n2);
         } else {
             hipLaunchKernelGGL((k_widths_reads<uint8_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, A, 1u, d_list2, d_n2);
             hipLaunchKernelGGL((k_widths_reads<uint8_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, A, 3u, d_list2, d_n2);
@@ -588,6 +647,7 @@ static int launch_pass(hsa_index *ix, const LaunchPlan &P0, SearchScratch &S, co
         size_t wblocks = ((size_t)n * 2 + BLOCK - 1) / BLOCK;
         if (wblocks < 1) wblocks = 1;
         if (P.wide) hipLaunchKernelGGL((k_widths<uint16_t, IT>), dim3((unsigned)wblocks), dim3(BLOCK), 0, st, A);
+        else if (P.snib) hipLaunchKernelGGL((k_widths<uint8_t, IT, true>), dim3((unsigned)wblocks), dim3(BLOCK), 0, st, A);
         else hipLaunchKernelGGL((k_widths<uint8_t, IT>), dim3((unsigned)wblocks), dim3(BLOCK), 0, st, A);
     }
     HSA_HIP(hipGetLastError());
@@ -601,8 +661,7 @@ static int launch_pass(hsa_index *ix, const LaunchPlan &P0, SearchScratch &S, co
         A.perm = d_perm;
     }
     if (ix->ev_split && first) HSA_HIP(hipEventRecord(ix->ev_split, st));   // the main pass only
-    if (P.wide) launch_search<uint16_t, IT>(P, A, st);
-    else launch_search<uint8_t, IT>(P, A, st);
+    launch_search<IT>(P, A, st);
     HSA_HIP(hipGetLastError());
     if (lazy) {
         // the forward pass: the forward rows and the forward-strand searches of the reads
@@ -613,10 +672,10 @@ static int launch_pass(hsa_index *ix, const LaunchPlan &P0, SearchScratch &S, co
         F.fwd_list = nullptr; F.fwd_n = nullptr; F.wkey = nullptr; F.perm = nullptr; F.rmap = nullptr;
         const unsigned rblocks = (unsigned)(((size_t)n + BLOCK - 1) / BLOCK);
         if (P.wide) hipLaunchKernelGGL((k_widths_reads<uint16_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, F, 2u, d_list2, d_n2);
+        else if (P.snib) hipLaunchKernelGGL((k_widths_reads<uint8_t, IT, true>), dim3(rblocks), dim3(BLOCK), 0, st, F, 2u, d_list2, d_n2);
         else hipLaunchKernelGGL((k_widths_reads<uint8_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, F, 2u, d_list2, d_n2);
         HSA_HIP(hipGetLastError());
-        if (P.wide) launch_search<uint16_t, IT>(P, F, st);
-        else launch_search<uint8_t, IT>(P, F, st);
+        launch_search<IT>(P, F, st);
         HSA_HIP(hipGetLastError());
     }
     if (split) {
@@ -695,12 +754,11 @@ template <typename IT = uint32_t>
 static int run_capacity_passes(hsa_index *ix, const RegimePlan &C, const PassIO &io, PassLink main, bool zero_ctr,
                                hipEvent_t ev_split, hipStream_t st)
 {
-    constexpr uint32_t EB = 4u * sizeof(IT);        // pool entry bytes
     LaunchPlan P, B, H;
     int rc;
-    if ((rc = plan_launch(ix, io.n, io.max_len, io.max_seed, C, PASS_MAIN, P, EB)) ||
-        (rc = plan_launch(ix, io.n, io.max_len, io.max_seed, C, PASS_BIG, B, EB)) ||
-        (rc = plan_launch(ix, io.n, io.max_len, io.max_seed, C, PASS_HUGE, H, EB)))
+    if ((rc = plan_launch<IT>(ix, io.n, io.max_len, io.max_seed, C, PASS_MAIN, P)) ||
+        (rc = plan_launch<IT>(ix, io.n, io.max_len, io.max_seed, C, PASS_BIG, B)) ||
+        (rc = plan_launch<IT>(ix, io.n, io.max_len, io.max_seed, C, PASS_HUGE, H)))
         return rc;
     if ((rc = hsa_grow(&ix->d_ovf, &ix->d_ovf_cap, (size_t)io.n * 4 + 64)) ||
         (rc = hsa_grow(&ix->d_ovf2, &ix->d_ovf2_cap, (size_t)io.n * 4 + 64)))

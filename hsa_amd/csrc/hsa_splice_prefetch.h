@@ -133,7 +133,7 @@ extern "C" int hsa_splice_seeds_device(hsa_index_t *ix, const hsa_regime_t *seed
     S.jobs = (hsa_job_t *)d; S.mg = (hsa_mg_job_t *)(d + o_mg); S.codes = (uint8_t *)(d + o_codes);
     S.cw = (int32_t *)(d + o_cw); S.list = (int32_t *)(d + o_list); S.count = cnt; S.ctr = ctr;
     RegimePlan C = regime_plan(seed_regime, 1);
-    C.nib_ok = false;
+    C.nib_ok = false; C.snib_ok = false;    // caller widths: byte rows
     if ((rc = stage_regimes(ix, seed_regime, 1, C.nb, st))) return rc;
     // the counters are zeroed here, before k_seed_prep adds the width queries to them
     HSA_HIP(hipMemsetAsync(ctr, 0, CTR_SLOTS * sizeof(unsigned long long), st));
@@ -527,7 +527,7 @@ static int pf_passes(hsa_index *ix, const PfSearch &F, bool anchors, int n_upper
     const PfArgs &A = F.A;
     const PfLayout &L = F.L;
     RegimePlan C = regime_plan(anchors ? F.anchor_rg : F.seed_rg, 1);
-    C.nb = F.nb; C.wide = F.wide; C.nib_ok = false;
+    C.nb = F.nb; C.wide = F.wide; C.nib_ok = false; C.snib_ok = false;
     // the caller widths are at rows + wb_off (a row's prefix, or cw + call * cws)
     const PassIO io{.jobs = A.jobs, .list = A.list + (anchors ? 6 * (size_t)A.n : 0), .n = n_upper, .codes = A.scodes,
                     .n_aln = A.call_n, .flags = A.call_fl, .hit_off = F.at<uint64_t>(L.call_hit),
