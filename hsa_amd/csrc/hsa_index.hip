@@ -61,11 +61,13 @@ extern "C" int hsa_configure(int waves_per_cu, int pool_entries, int hit_cap)
     return 0;
 }
 
-// HSA_VERBOSE: device allocations that take more than 5 ms (a first batch's stall)
+// HSA_VERBOSE: device allocations that take more than 5 ms (a first batch's stall);
+// HSA_VERBOSE=2: every one (tests: a pass after the warm-up allocates nothing)
 static void hsa_log_alloc(const char *what, size_t bytes, std::chrono::steady_clock::time_point t0)
 {
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (ms > 5.0 && getenv("HSA_VERBOSE")) fprintf(stderr, "[hsa] %s: hipMalloc of %.2f GB took %.1f ms\n", what, bytes / 1e9, ms);
+    const char *v = getenv("HSA_VERBOSE");
+    if (v && (ms > 5.0 || atoi(v) >= 2)) fprintf(stderr, "[hsa] %s: hipMalloc of %.2f GB took %.1f ms\n", what, bytes / 1e9, ms);
 }
 
 // A new device buffer of `bytes` in *out, and the old one (*old, contents not kept)
@@ -110,9 +112,7 @@ int hsa_grow(void **p, size_t *cap, size_t need)
 void hsa_scratch_free(SearchScratch &s)
 {
     (void)hipFree(s.pool); (void)hipFree(s.nxt); (void)hipFree(s.hbuf);
-    const size_t lb = s.link_bytes;
     s = SearchScratch();
-    s.link_bytes = lb;
 }
 
 extern "C" int hsa_index_release_scratch(hsa_index_t *ix)
@@ -145,19 +145,25 @@ int hsa_scratch_reserve(SearchScratch &s, size_t lanes, size_t pcap, size_t hcap
         hsa_scratch_free(s);
         return HSA_E_MEM;
     };
-    if (!s.pool || pe > s.pool_entries || link_bytes != s.link_bytes) {
+    // The link array is as wide as the widest pass so far needs (0: passes whose entries
+    // carry their links reserve none), and widening it leaves the pool where it is: a handle
+    // that alternates gapped and ungapped searches reallocates nothing after its first of each.
+    const size_t lbn = link_bytes > s.link_bytes ? link_bytes : s.link_bytes;
+    const bool grow = !s.pool || pe > s.pool_entries;
+    if (grow || lbn != s.link_bytes) {
         const size_t npe = pe > s.pool_entries ? pe : s.pool_entries;
         const auto t0 = std::chrono::steady_clock::now();
         void *np = nullptr, *nn = nullptr;
-        if (hsa_realloc_device(&np, (void **)&s.pool, npe * sizeof(uint4)) ||
-            hsa_realloc_device(&nn, &s.nxt, npe * link_bytes)) {
+        if ((grow && hsa_realloc_device(&np, (void **)&s.pool, npe * sizeof(uint4))) ||
+            (lbn && hsa_realloc_device(&nn, &s.nxt, npe * lbn))) {
             (void)hipFree(np);
             return fail();
         }
-        s.pool = (uint4 *)np; s.nxt = nn;
+        if (grow) s.pool = (uint4 *)np;
+        if (lbn) s.nxt = nn;
         s.pool_entries = npe;
-        s.link_bytes = link_bytes;
-        hsa_log_alloc("search scratch pool", npe * (sizeof(uint4) + link_bytes), t0);
+        s.link_bytes = lbn;
+        hsa_log_alloc("search scratch pool", npe * ((grow ? sizeof(uint4) : 0) + lbn), t0);
     }
     if (!s.hbuf || he > s.hit_entries) {
         const size_t nhe = he > s.hit_entries ? he : s.hit_entries;

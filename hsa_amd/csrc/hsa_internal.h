@@ -50,9 +50,10 @@ enum : uint32_t {
 struct SearchScratch {
     size_t pool_entries = 0, hit_entries = 0;
     uint4 *pool = nullptr;       // pool_entries
-    void *nxt = nullptr;         // pool_entries links: uint16_t (main, big passes) or uint32_t (huge pass)
+    void *nxt = nullptr;         // pool_entries links of link_bytes each: uint16_t (main, big passes), uint32_t
+                                 //   (huge pass), none while every pass kept its links in the entries
     uint32_t *hbuf = nullptr;    // hit_entries * 9
-    size_t link_bytes = 2;
+    size_t link_bytes = 0;       // the widest link any pass reserved so far
 };
 
 struct hsa_index {

@@ -29,8 +29,9 @@
 // (everything bwt_match_gap's pruning reads: bwtgap.c:170, :256-263) and the
 // stack's bucket heads.  Buckets are the REACHABLE scores only (a score table per
 // regime maps aln_score -> dense bucket, order preserved), so `-n 4 -o 0` needs 6
-// heads instead of the reference's 54 (bwtgap.c:18).  Stack entries (16 bytes + a
-// 16-bit link) live in a per-lane pool in HBM; a bit mask in registers gives the
+// heads instead of the reference's 54 (bwtgap.c:18).  Stack entries (16 bytes and a
+// 16-bit link: inside the entry where it has room, pool_link_in_entry, else in a link
+// array) live in a per-lane pool in HBM; a bit mask in registers gives the
 // lowest non-empty bucket (== gap_stack_t.best).  The child pushed LAST by an
 // expansion is always the next pop when its bucket is the lowest, so it stays in
 // registers ("virtual top").  A regime set without gap opens (max_gapo == 0: every
@@ -78,7 +79,7 @@ struct SearchArgs {
     uint32_t *wg;                  //   64 rows interleaved; wg: full w values (gap_shadow only)
     uint32_t rb, rs, rg;           //   row capacities: bytes, bytes, words
     uint4 *pool;
-    void *nxt;                     // pool links: uint16_t, or uint32_t in the huge pass
+    void *nxt;                     // pool links: uint16_t, or uint32_t in the huge pass (unused where the entries hold them)
     uint32_t *hbuf;
     uint32_t pcap, hcap, nb;
     uint32_t off_heads, off_wb, off_ws;   // LDS byte offsets
@@ -177,11 +178,34 @@ __device__ __forceinline__ ColdArgs cold_args()
 }
 
 // entry meta word: i:10 | state:2 | is_diff:1 | n_mm:7 | n_gapo:4 | n_gape:8
-__device__ __forceinline__ uint32_t meta_pack(uint32_t i, uint32_t st, uint32_t isd, uint32_t mm, uint32_t go,
-                                              uint32_t ge)
+constexpr __host__ __device__ __forceinline__ uint32_t meta_pack(uint32_t i, uint32_t st, uint32_t isd, uint32_t mm,
+                                                                 uint32_t go, uint32_t ge)
 {
     return i | st << 10 | isd << 12 | mm << 13 | go << 20 | ge << 24;
 }
+// The pool form of an ungapped entry's meta word when its bucket-list link travels with
+// it (k_search's LK, 32-bit intervals): i:10 | is_diff:1 | n_mm:5 | link:16.  State is
+// ST_M and both gap counts are 0 there, and n_mm <= 15 (8- and 4-bit rows exist only
+// while every bid bound is <= 14).  Registers keep meta_pack's layout.
+constexpr __host__ __device__ __forceinline__ uint32_t meta_link_pack(uint32_t m, uint32_t link)
+{
+    return (m & 1023u) | ((m >> 12) & 1u) << 10 | ((m >> 13) & 31u) << 11 | link << 16;
+}
+constexpr __host__ __device__ __forceinline__ uint32_t meta_link_meta(uint32_t w)
+{
+    return (w & 1023u) | ((w >> 10) & 1u) << 12 | ((w >> 11) & 31u) << 13;
+}
+constexpr __host__ __device__ __forceinline__ uint32_t meta_link_next(uint32_t w) { return w >> 16; }
+#define META_LINK_RT(i, isd, mm, link)                                                                      \
+    (meta_link_meta(meta_link_pack(meta_pack(i, ST_M, isd, mm, 0, 0), link)) == meta_pack(i, ST_M, isd, mm, 0, 0) && \
+     meta_link_next(meta_link_pack(meta_pack(i, ST_M, isd, mm, 0, 0), link)) == (link))
+static_assert(META_LINK_RT(1023u, 1u, 31u, 0u), "entry link: round trip at the field limits");
+static_assert(META_LINK_RT(1023u, 1u, 31u, 0xFFFEu), "entry link: round trip at the field limits");
+static_assert(META_LINK_RT(1023u, 1u, 31u, NIL16), "entry link: round trip at the field limits");
+static_assert(META_LINK_RT(0u, 0u, 0u, NIL16) && META_LINK_RT(0u, 0u, 0u, 0u), "entry link: round trip of zero fields");
+static_assert(META_LINK_RT(1023u, 0u, 0u, 0x8000u) && META_LINK_RT(0u, 1u, 0u, 0u) && META_LINK_RT(0u, 0u, 31u, 0u),
+              "entry link: each field alone");
+#undef META_LINK_RT
 #define M_I(m) ((int)((m) & 1023u))
 #define M_ST(m) ((int)(((m) >> 10) & 3u))
 #define M_ISD(m) ((int)(((m) >> 12) & 1u))
@@ -239,6 +263,18 @@ template <typename IT> struct Ent {
 #ifndef HSA_POOL_CHUNK
 #define HSA_POOL_CHUNK 1
 #endif
+#ifndef HSA_POOL_LINK
+#define HSA_POOL_LINK 1       // A/B builds: -DHSA_POOL_LINK=0 keeps every pass's links in the link array
+#endif
+// The passes whose pool entries carry their bucket-list link (k_search's LK; the launch
+// plan reserves no link array for them): every pass but HUGE, whose free list rewrites
+// links, of 64-bit intervals (the entry has a spare word) and of 32-bit ungapped searches
+// with 8- or 4-bit rows (the meta word has 16 spare bits, meta_link_pack).  The gapped
+// 32-bit searches (a full meta word) and the 16-bit rows keep the link array.
+constexpr __host__ __device__ bool pool_link_in_entry(bool huge, bool it64, bool gaps, bool rows16)
+{
+    return HSA_POOL_LINK && !huge && (it64 || (!gaps && !rows16));
+}
 // Slot s of a lane's pool.  Default: uint4 element base + s * 64 (32-bit entries) or the
 // two elements base + s * 128 and base + s * 128 + 64 (64-bit entries); base (pool_base)
 // is the lane's slot 0, computed once per launch.  HSA_POOL_CHUNK: 64-byte chunks of
@@ -287,6 +323,36 @@ __device__ __forceinline__ void ent_store(uint4 *pool, size_t base, uint32_t slo
     } else {
         pool[i] = make_uint4((uint32_t)e.x, (uint32_t)(e.x >> 32), (uint32_t)e.y, (uint32_t)(e.y >> 32));
         pool[i + (HSA_POOL_CHUNK ? 1 : 64)] = make_uint4((uint32_t)e.z, (uint32_t)(e.z >> 32), e.w, 0u);
+    }
+}
+// The same with the entry's 16-bit bucket-list link inside it (k_search's LK): in the
+// meta word's upper half (32-bit entries, meta_link_pack) or in the second element's
+// last word, which ent_store leaves 0 (64-bit entries).  One sector per pop, one store
+// per push, and no link array.
+template <typename IT>
+__device__ __forceinline__ Ent<IT> ent_load_link(const uint4 *pool, size_t base, uint32_t slot, uint32_t &link)
+{
+    const size_t i = ent_at<IT>(base, slot);
+    if constexpr (sizeof(IT) == 4) {
+        const uint4 v = pool[i];
+        link = meta_link_next(v.w);
+        return Ent<IT>{v.x, v.y, v.z, meta_link_meta(v.w)};
+    } else {
+        const uint4 u = pool[i], v = pool[i + (HSA_POOL_CHUNK ? 1 : 64)];
+        link = v.w;
+        return Ent<IT>{(uint64_t)u.x | (uint64_t)u.y << 32, (uint64_t)u.z | (uint64_t)u.w << 32,
+                       (uint64_t)v.x | (uint64_t)v.y << 32, v.z};
+    }
+}
+template <typename IT>
+__device__ __forceinline__ void ent_store_link(uint4 *pool, size_t base, uint32_t slot, const Ent<IT> &e, uint32_t link)
+{
+    const size_t i = ent_at<IT>(base, slot);
+    if constexpr (sizeof(IT) == 4) {
+        pool[i] = make_uint4(e.x, e.y, e.z, meta_link_pack(e.w, link));
+    } else {
+        pool[i] = make_uint4((uint32_t)e.x, (uint32_t)(e.x >> 32), (uint32_t)e.y, (uint32_t)(e.y >> 32));
+        pool[i + (HSA_POOL_CHUNK ? 1 : 64)] = make_uint4((uint32_t)e.z, (uint32_t)(e.z >> 32), e.w, link);
     }
 }
 // staged words per hit (HB) and words per output hit record: bwt_aln1_t (bwtaln.h:41-50)
@@ -795,6 +861,9 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
     // the 64-bit 4-bit-row kernels spilled with it)
     constexpr bool FRH = !HUGE && HSA_HELPERS && GAPS && sizeof(IT) == 4 && !WFmt<WT>::NIB;
     constexpr uint32_t NIL = HUGE ? 0xFFFFFFFFu : (uint32_t)NIL16;
+    // the link of a pool entry inside the entry (pool_link_in_entry): a link is written once,
+    // at the push, with the bucket's old head, so it costs no sector of its own
+    constexpr bool LK = pool_link_in_entry(HUGE, sizeof(IT) == 8, GAPS, std::is_same<WT, uint16_t>::value);
     // the implicit root levels (SearchArgs::sdc, hsa_trie.h).  Without indels an entry at
     // read position i stands for a string of exactly len - i characters, and on a level of
     // which every string occurs nothing reads its interval: a read longer than sdc keeps
@@ -947,6 +1016,23 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
     };
     // push to the pool (gap_push, bwtgap.c:46-75)
     auto flush = [&](const E &v, int b) {
+        if constexpr (LK) {
+            // one store, the old head folded in.  (The overflow bit is set on one path for
+            // both outcomes: with `ctl |= bit; return` beside `mask.set(b)` the compiler merged
+            // the two updates into one store through a selected address, and ctl and the mask
+            // went to the private segment.)
+            uint32_t ovf = 1u;
+            if ((uint32_t)b < a.nb && pool_top < a.pcap) {
+                const uint32_t slot = pool_top++;
+                DC(8);
+                ent_store_link<IT>(a.pool, pbase, slot, v, mask.test(b) ? (uint32_t)HEAD(b) : NIL);
+                HEAD(b) = (LT)slot;
+                mask.set(b);
+                ovf = 0u;
+            }
+            ctl |= ovf << 8;
+            return;
+        }
         if ((uint32_t)b >= a.nb) { ctl |= 1u << 8; return; }
         uint32_t slot;
         if (HUGE && free_head != NIL) {
@@ -1568,8 +1654,13 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
                 // pop the head of the lowest non-empty bucket
                 const int b = mask.lowest();
                 const uint32_t slot = HEAD(b);
-                e = ent_load<IT>(a.pool, pbase, slot);
-                const uint32_t nx = NXT(slot);
+                uint32_t nx;
+                if constexpr (LK) {
+                    e = ent_load_link<IT>(a.pool, pbase, slot, nx);
+                } else {
+                    e = ent_load<IT>(a.pool, pbase, slot);
+                    nx = NXT(slot);
+                }
                 if (nx == NIL) mask.reset(b);
                 else HEAD(b) = (LT)nx;
                 if (HUGE) { NXT(slot) = (LT)free_head; free_head = slot; }
@@ -1801,7 +1892,7 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
                     // match child has the parent's.  The groups' bucket heads are kept in
                     // registers across the loop (equal buckets updated together, so the
                     // links are flush()'s) and written back once: the divergent loop does
-                    // two stores per candidate and no LDS round trip.
+                    // one store per candidate (two with a link array) and no LDS round trip.
                     const uint32_t g_go = (uint32_t)ego + (est == ST_M), g_ge = (uint32_t)ege + (est != ST_M);
                     const uint32_t mI = meta_pack((uint32_t)i, ST_I, 1u, (uint32_t)emm, g_go, g_ge);
                     const uint32_t mD = meta_pack((uint32_t)(i + 1), ST_D, 1u, (uint32_t)emm, g_go, g_ge);
@@ -1828,8 +1919,12 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
                         if ((uint32_t)bk >= a.nb || pool_top >= a.pcap) { ctl |= 1u << 8; continue; }
                         const uint32_t slot = pool_top++;
                         DC(8);
-                        ent_store<IT>(a.pool, pbase, slot, E{k, l, rk, meta});
-                        NXT(slot) = (LT)(bk == bG ? hG : bk == bM ? hM : hP);
+                        if constexpr (LK) {
+                            ent_store_link<IT>(a.pool, pbase, slot, E{k, l, rk, meta}, bk == bG ? hG : bk == bM ? hM : hP);
+                        } else {
+                            ent_store<IT>(a.pool, pbase, slot, E{k, l, rk, meta});
+                            NXT(slot) = (LT)(bk == bG ? hG : bk == bM ? hM : hP);
+                        }
                         hG = bk == bG ? slot : hG;
                         hM = bk == bM ? slot : hM;
                         hP = bk == bP ? slot : hP;

@@ -152,6 +152,10 @@ static SearchFn search_kernel(const LaunchPlan &P)
     return P.nt == 64 ? search_kernel_nt<uint8_t, 64, IT, false>(P) : search_kernel_nt<uint8_t, 256, IT, false>(P);
 }
 
+// Whether the plan's k_search instantiation keeps each pool entry's link in the entry
+// (k_search's LK); EW: 32-bit words per interval bound.
+static bool plan_entry_links(const LaunchPlan &P, size_t EW) { return pool_link_in_entry(P.huge, EW == 2, P.gaps, P.wide); }
+
 // Waves per SIMD a kernel's registers allow: gfx950 gives a wave its VGPRs in granules of 8
 // out of 512 per lane, at most 8 waves.  Asked of the runtime once per instantiation; 4,
 // what k_search's launch bound guarantees, where it does not say.
@@ -299,8 +303,9 @@ static int plan_launch(hsa_index *ix, int n_jobs, int max_len, int max_seed, con
         int occ = 0;
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_search<1, true, uint8_t, 256>, 256, P.lds);
         fprintf(stderr, "[hsa] launch: %d CUs x %d workgroups of %u lanes (runtime occupancy query says %d), "
-                "LDS %zu B, %zu workgroups, %d buckets%s\n", ix->n_cu, per_cu, P.nt, occ, P.lds, blocks, nb,
-                P.nib ? ", 4-bit rows" : P.snib ? ", 4-bit seed row" : "");
+                "LDS %zu B, %zu workgroups, %d buckets%s%s\n", ix->n_cu, per_cu, P.nt, occ, P.lds, blocks, nb,
+                P.nib ? ", 4-bit rows" : P.snib ? ", 4-bit seed row" : "",
+                plan_entry_links(P, sizeof(IT) / 4) ? ", links in the entries" : "");
     }
     // pool slots are not reused within a search: gapped searches push many more.  A
     // deeper main-pass pool keeps the long gapped searches inside the main pass, where
@@ -511,15 +516,30 @@ static int help_args(hsa_index *ix, SearchArgs &A, size_t items, const LaunchPla
 // bound is max_entries, bwtgap.c:150-151, which the HUGE pass keeps).
 static int scratch_fit(hsa_index *ix, SearchScratch &S, LaunchPlan &P, size_t EW)
 {
-    const size_t lb = P.huge ? 4 : 2, floor_cap = 512;
+    // link bytes per pool entry: none where the pass's kernel keeps the links in the entries;
+    // the scratch's link array stays as wide as an earlier pass made it (hsa_scratch_reserve)
+    const size_t lb = P.huge ? 4 : plan_entry_links(P, EW) ? 0 : 2, floor_cap = 512;
+    const size_t lba = lb > S.link_bytes ? lb : S.link_bytes;
     auto pe_of = [&](uint32_t pc) { return (size_t)((pc + 31u) & ~31u) * EW; };
     const size_t rl = P.res_lanes > P.lanes ? P.res_lanes : P.lanes;
-    auto bytes = [&](uint32_t pc) { return rl * (pe_of(pc) * (16 + lb) + (size_t)P.hcap * EW * 36); };
-    const bool held = S.pool && lb == S.link_bytes && rl * pe_of(P.pcap) <= S.pool_entries &&
-                      rl * (size_t)P.hcap * EW <= S.hit_entries;
+    auto bytes = [&](uint32_t pc) { return rl * (pe_of(pc) * (16 + lba) + (size_t)P.hcap * EW * 36); };
+    const char *cm = getenv("HSA_SCRATCH_MB");          // read per pass: tests set it mid-process
+    const size_t cap_mb = cm ? strtoull(cm, nullptr, 10) : 0;
+    const bool fits = S.pool && rl * pe_of(P.pcap) <= S.pool_entries && rl * (size_t)P.hcap * EW <= S.hit_entries;
+    bool held = fits && lb <= S.link_bytes;
+    if (fits && !held && !P.huge) {
+        // Only the link array widens: hsa_scratch_reserve allocates it for the pool the handle
+        // holds (S.pool_entries, which may exceed this pass's) and leaves that pool in place.
+        // Where that does not fit beside the pool, the scratch is given back first and the
+        // pool and its links are planned together below, from what is then free.
+        size_t fr = 0, tot = 0;
+        if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = (size_t)-1 / 2; }
+        const size_t need = S.pool_entries * lb + ((size_t)2 << 30);     // the old array is freed after the new one exists
+        const size_t all = S.pool_entries * (16 + lb) + S.hit_entries * 36;
+        if (need <= fr && !(cap_mb && all > (cap_mb << 20))) held = true;
+        else hsa_scratch_free(S);
+    }
     if (!held && !P.huge) {
-        const char *cm = getenv("HSA_SCRATCH_MB");      // read per pass: tests set it mid-process
-        const size_t cap_mb = cm ? strtoull(cm, nullptr, 10) : 0;
         size_t fr = 0, tot = 0;
         if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = (size_t)-1 / 2; }
         fr += S.pool_entries * (16 + S.link_bytes) + S.hit_entries * 36;     // what the reservation frees first

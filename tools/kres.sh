@@ -15,5 +15,6 @@ for m in re.finditer(r'\.name:\s+(\S+)\n(.*?)\.wavefront_size', s, re.S):
     g = lambda k: re.search(k + r':\s+(\d+)', body).group(1)
     fn = re.search(r'\n' + re.escape(name) + r':(.*?)s_endpgm', s, re.S)
     n = sum(1 for l in fn.group(1).split('\n') if l.startswith('\t') and not l.startswith('\t.') and not l.startswith('\t;')) if fn else -1
-    print(f"{name[:60]:60s} sgpr {g('sgpr_count'):>3} spill {g('sgpr_spill_count'):>3}  vgpr {g('vgpr_count'):>3} spill {g('vgpr_spill_count'):>3}  insts {n}")
+    # scratch: the private segment in bytes (register spills, and arrays or merged stores the compiler lowered to it)
+    print(f"{name[:60]:60s} sgpr {g('sgpr_count'):>3} spill {g('sgpr_spill_count'):>3}  vgpr {g('vgpr_count'):>3} spill {g('vgpr_spill_count'):>3}  scratch {g('private_segment_fixed_size'):>3}  insts {n}")
 PY
