@@ -122,7 +122,7 @@ struct SearchArgs {
     uint8_t *wkey;
     const int32_t *perm;
     uint32_t okey;                  // cost key with the tail length (default; HSA_ORDER_KEY=0: bid only)
-    // lazy forward rows (k_widths_reads): a read whose rc search found nothing and whose
+    // lazy forward rows (k_widths_lazy): a read whose rc search found nothing and whose
     // forward row was not computed goes to fwd_list (count *fwd_n); the forward pass
     // (fwd_only) searches just that strand
     int32_t *fwd_list;
@@ -603,6 +603,23 @@ __device__ __forceinline__ void wave_add(unsigned long long *c, unsigned long lo
 
 #define HSA_NOFWD 0xFFFFFFFFu        // wq: this read's forward row was not computed
 #define HSA_F_NEEDFWD 0x100u         // k_search internal: rc had no hit, forward row missing
+// wq's two high bits (a row's query count stays far below 2^30, so no flagged value equals
+// HSA_NOFWD): the strand's search cannot have a hit, because the bid of its last base
+// exceeds max_diff and bwt_match_gap prunes the root at its first pop (bwtgap.c:170).
+// k_search counts that pop and starts no such strand (begin_item).
+#define HSA_WQ_RC_DOOMED 0x80000000u
+#define HSA_WQ_FWD_DOOMED 0x40000000u
+#define HSA_WQ_COUNT 0x3FFFFFFFu
+#ifndef HSA_DOOM_SKIP
+#define HSA_DOOM_SKIP 1                    // A/B builds: -DHSA_DOOM_SKIP=0 starts every strand
+#endif
+#ifndef HSA_LAZY_MIN_LEN
+#define HSA_LAZY_MIN_LEN 100               // lazy forward rows by default for reads this long (launch_pass) ...
+#endif
+#define HSA_LAZY_MIN_LEN_GAPPED 200        // ... and in searches with gap opens
+
+// the root of a row's search is pruned: width[len - 1].bid = w.bid - 1 > max_diff
+__device__ __forceinline__ bool row_doomed(const WRow &w, const hsa_job_t &J) { return (int)w.bid - 1 > J.max_diff; }
 
 // One lane per row (rows in order): row = list position * 2 + strand.  The forward
 // strand's rows are computed speculatively and count as the reference's work only
@@ -614,12 +631,17 @@ __global__ void __launch_bounds__(BLOCK) k_widths(SearchArgs a)
     const uint32_t n_jobs = a.n_dev ? (uint32_t)*a.n_dev : (uint32_t)a.n_jobs;
     const uint32_t q = R >> 1, strand = R & 1u;
     WRow w{0, 0, 0, 0};
+    uint32_t doomed = 0;
     if (R < 2u * n_jobs) {
         const hsa_job_t J = a.jobs[a.job_list ? a.job_list[q] : (int)q];
         w = width_row<WT, IT, SN>(a, R, strand, J);
-        if (!strand) a.wq[q] = w.q;
+        doomed = row_doomed(w, J) ? 1u : 0u;
         if (a.wkey) a.wkey[R] = cost_key(a, w);
     }
+    // a read's two rows are neighbouring lanes: the forward lane writes both flags
+    const uint32_t rc_doomed = (uint32_t)__shfl_xor((int)doomed, 1);
+    if (R < 2u * n_jobs && !strand)
+        a.wq[q] = w.q | (rc_doomed ? HSA_WQ_RC_DOOMED : 0u) | (doomed ? HSA_WQ_FWD_DOOMED : 0u);
     // rank queries: the reverse-complement strand is always searched (bwtaln.c:343)
     wave_add(&a.ctr[CTR_RANK], strand ? w.q : 0u);
     wave_add(&a.ctr[CTR_WIDTH_Q], strand ? w.q : 0u);
@@ -628,53 +650,83 @@ __global__ void __launch_bounds__(BLOCK) k_widths(SearchArgs a)
     wave_add(&a.ctr[CTR_TRIE], w.t);
 }
 
-// One lane per read, one strand's row each.
-// mode 1 (main pass of a large batch): the rc row of every read; a read whose rc search
-//   cannot have a hit -- its root is pruned when the last base's bid exceeds max_diff
-//   (bwtgap.c:170) -- goes to list2 for its forward row; the others get wq = HSA_NOFWD
-//   and k_search hands them to the forward pass if rc finds nothing (bwtaln.c:343-359).
-// mode 3: the forward rows of list2 (the speculative count, as k_widths').
-// mode 2 (the forward pass): the forward rows of the reads k_search listed, the
-//   reference's work.
+// The lazy main pass of a large batch, one launch: the rc row of every read, and the
+// forward row of the reads whose rc search cannot have a hit (row_doomed); the others get
+// wq = HSA_NOFWD and k_search hands them to the forward pass if rc finds nothing
+// (bwtaln.c:343-359).  A workgroup takes BLOCK reads: every lane computes its read's rc row
+// into the rc plane (row q); the doomed reads are compacted through LDS (a ballot per wave,
+// the waves' counts and lists in LDS, one barrier), and lanes 0 .. k - 1 compute their
+// forward rows into the forward plane at the workgroup's own place, row
+// n_al + blockIdx.x * BLOCK + i (rmap[q]), so a step's stores stay one coalesced wave store
+// per word and nothing is shared between workgroups.  A wave left without a row only adds its counts.
+// The forward rows here are speculative (CTR_FWD_Q_ALL), as k_widths' are.
 template <typename WT, typename IT = uint32_t, bool SN = false>
-__global__ void __launch_bounds__(BLOCK) k_widths_reads(SearchArgs a, uint32_t mode, int32_t *list2,
-                                                        unsigned long long *n2)
+__global__ void __launch_bounds__(BLOCK) k_widths_lazy(SearchArgs a)
 {
-    const uint32_t p = blockIdx.x * BLOCK + threadIdx.x;
-    const uint32_t n_jobs = mode == 3 ? (uint32_t)*n2 : a.n_dev ? (uint32_t)*a.n_dev : (uint32_t)a.n_jobs;
-    WRow w{0, 0, 0, 0};
+    __shared__ uint32_t s_cnt[BLOCK / 64];
+    __shared__ uint8_t s_src[BLOCK];                  // wave w's doomed reads (lane numbers in the workgroup) at w * 64
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t q = blockIdx.x * BLOCK + tid;
+    const uint32_t n_jobs = (uint32_t)a.n_jobs;
+    const uint32_t n_al = (n_jobs + 63u) & ~63u;
+    uint32_t rq = 0, sq = 0, sb = 0, stt = 0;
     bool more = false;
-    if (p < n_jobs) {
-        const uint32_t q = mode == 3 ? (uint32_t)list2[p] : p;
+    if (q < n_jobs) {
         const hsa_job_t J = a.jobs[a.job_list ? a.job_list[q] : (int)q];
-        // mode 1: the rc plane (row q); mode 3: the forward plane after it (row n_al + p);
-        // mode 2 (forward pass, no plane map): row 2 p
-        const uint32_t R = mode == 1 ? q : mode == 3 ? (uint32_t)(((uint32_t)a.n_jobs + 63u) & ~63u) + p : 2u * q;
-        w = width_row<WT, IT, SN>(a, R, mode == 1 ? 1u : 0u, J);
-        if (mode == 3) a.rmap[q] = (int32_t)R;
-        const uint8_t key = cost_key(a, w);
-        if (mode == 1) {
-            more = (int)w.bid - 1 > J.max_diff;
+        const WRow w = width_row<WT, IT, SN>(a, q, 1u, J);
+        more = row_doomed(w, J);
+        rq = w.q; sb = w.b; stt = w.t;
+        if (a.wkey) a.wkey[2 * q + 1] = cost_key(a, w);
+        if (!more) {
             a.wq[q] = HSA_NOFWD;
-            if (a.wkey) { a.wkey[2 * q + 1] = key; a.wkey[2 * q] = 255u; }
-        } else if (mode == 3) {
-            a.wq[q] = w.q;
-            if (a.wkey) a.wkey[2 * q] = key;
+            if (a.wkey) a.wkey[2 * q] = 255u;
         }
     }
-    if (mode == 1) {                                    // list2: one atomic per wave
-        const uint64_t m = __ballot(more);
-        const int lane = (int)(threadIdx.x & 63);
-        unsigned long long b = 0;
-        if (m && lane == __ffsll((unsigned long long)m) - 1) b = atomicAdd(n2, (unsigned long long)__popcll(m));
-        b = __shfl(b, __ffsll((unsigned long long)(m ? m : 1ull)) - 1);
-        if (more) list2[b + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)p;
+    const uint64_t m = __ballot(more);
+    if (lane == 0) s_cnt[wave] = (uint32_t)__popcll(m);
+    if (more) s_src[wave * 64u + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint8_t)tid;
+    __syncthreads();
+    // lane i takes the i-th doomed read of the workgroup, in wave order
+    uint32_t k = 0, src = BLOCK;
+    for (uint32_t v = 0; v < BLOCK / 64; ++v) {
+        const uint32_t c = s_cnt[v];
+        if (tid >= k && tid < k + c) src = s_src[v * 64u + (tid - k)];
+        k += c;
     }
-    const uint32_t rq = mode == 1 ? w.q : 0u, fq = mode == 2 ? w.q : 0u, sq = mode == 3 ? w.q : 0u;
-    wave_add(&a.ctr[CTR_RANK], rq + fq);
-    wave_add(&a.ctr[CTR_WIDTH_Q], rq + fq);
-    wave_add(&a.ctr[CTR_FWD_Q_ALL], fq + sq);
-    wave_add(&a.ctr[CTR_FWD_Q_REF], fq);
+    if (wave * 64u < k && src < BLOCK) {
+        const uint32_t q2 = blockIdx.x * BLOCK + src;
+        const hsa_job_t J = a.jobs[a.job_list ? a.job_list[q2] : (int)q2];
+        const uint32_t R = n_al + blockIdx.x * BLOCK + tid;
+        const WRow w = width_row<WT, IT, SN>(a, R, 0u, J);
+        a.rmap[q2] = (int32_t)R;
+        a.wq[q2] = w.q | HSA_WQ_RC_DOOMED | (row_doomed(w, J) ? HSA_WQ_FWD_DOOMED : 0u);
+        if (a.wkey) a.wkey[2 * q2] = cost_key(a, w);
+        sq = w.q; sb += w.b; stt += w.t;
+    }
+    wave_add(&a.ctr[CTR_RANK], rq);
+    wave_add(&a.ctr[CTR_WIDTH_Q], rq);
+    wave_add(&a.ctr[CTR_FWD_Q_ALL], sq);
+    wave_add(&a.ctr[CTR_SECTORS], sb);
+    wave_add(&a.ctr[CTR_TRIE], stt);
+}
+
+// The forward pass of a lazy search: one lane per read k_search listed, its forward row
+// (row 2 p, no plane map), the reference's work.
+template <typename WT, typename IT = uint32_t, bool SN = false>
+__global__ void __launch_bounds__(BLOCK) k_widths_fwd(SearchArgs a)
+{
+    const uint32_t p = blockIdx.x * BLOCK + threadIdx.x;
+    const uint32_t n_jobs = a.n_dev ? (uint32_t)*a.n_dev : (uint32_t)a.n_jobs;
+    WRow w{0, 0, 0, 0};
+    if (p < n_jobs) {
+        const hsa_job_t J = a.jobs[a.job_list ? a.job_list[p] : (int)p];
+        w = width_row<WT, IT, SN>(a, 2u * p, 0u, J);
+        a.wq[p] = w.q | (row_doomed(w, J) ? HSA_WQ_FWD_DOOMED : 0u);
+    }
+    wave_add(&a.ctr[CTR_RANK], w.q);
+    wave_add(&a.ctr[CTR_WIDTH_Q], w.q);
+    wave_add(&a.ctr[CTR_FWD_Q_ALL], w.q);
+    wave_add(&a.ctr[CTR_FWD_Q_REF], w.q);
     wave_add(&a.ctr[CTR_SECTORS], w.b);
     wave_add(&a.ctr[CTR_TRIE], w.t);
 }
@@ -815,7 +867,7 @@ static __global__ void __launch_bounds__(BLOCK) k_split_finalize(SearchArgs a)
             na = nr; off = a.sp_off[2 * q];
             q_add = a.sp_q[2 * q]; p_add = a.sp_p[2 * q];
         } else {
-            w_add = a.wq[q];
+            w_add = a.wq[q] & HSA_WQ_COUNT;
             q_add = (unsigned long long)a.sp_q[2 * q] + a.sp_q[2 * q + 1] + w_add;
             p_add = (unsigned long long)a.sp_p[2 * q] + a.sp_p[2 * q + 1];
             if (nf > 0) { na = nf; off = a.sp_off[2 * q + 1]; }
@@ -1218,7 +1270,7 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
                 finish_job(HSA_F_NEEDFWD, 0, 0);   // its forward row is computed by the forward pass
             } else {
                 ctl &= ~(1u << 3);          // strand 0
-                st_wq += wq;                // its widths are the reference's work now (bwtaln.c:344-348)
+                st_wq += wq & HSA_WQ_COUNT; // its widths are the reference's work now (bwtaln.c:344-348)
                 start_strand();
             }
         } else {
@@ -1346,6 +1398,25 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
         pen = (uint32_t)R->s_mm | (uint32_t)R->s_gapo << 10 | (uint32_t)R->s_gape << 20;
         rmode = (uint32_t)R->mode | (uint32_t)R->max_gapo << 8 | (uint32_t)R->max_gape << 16;
         if (opt_max_diff > R->max_diff) ctl |= 2u << 8;
+        if constexpr (HSA_DOOM_SKIP) {
+            // an ordinary two-strand item whose rc root is pruned at its first pop (k_widths'
+            // flag in wq): that pop is counted here and the forward strand starts at once, as
+            // end_strand would start it a batch of (A) later; with the forward root pruned as
+            // well the read ends here, without a row copy.  (Selects and one branch: each
+            // nested divergent branch here costs the 64-bit kernels a saved exec mask they
+            // have no SGPRs for.)
+            uint32_t wq = HSA_NOFWD;
+            if (!r->mg && !r->split && !r->fwd_only) wq = r->wq[qpos];      // uniform conditions
+            const bool rcd = wq != HSA_NOFWD && (wq & HSA_WQ_RC_DOOMED) != 0u && !C_OVF(ctl);
+            const bool both = rcd && (wq & HSA_WQ_FWD_DOOMED) != 0u;
+            st_p += (rcd ? 1u : 0u) + (both ? 1u : 0u);
+            ctl &= ~(rcd ? 8u : 0u);                         // strand 0
+            st_wq += rcd ? wq & HSA_WQ_COUNT : 0u;           // its widths are the reference's work (bwtaln.c:344-348)
+            if (both) {
+                finish_job(HSA_F_FALLBACK, 0, 0);
+                return;
+            }
+        }
         start_strand();
     };
     // helpers: publish this strand's live entries -- the virtual top, then every bucket's

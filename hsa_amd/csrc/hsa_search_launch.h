@@ -631,38 +631,32 @@ static int launch_pass(hsa_index *ix, const LaunchPlan &P0, SearchScratch &S, co
     }
     // lazy forward rows: the main pass of a batch searched one read per lane computes a
     // read's forward row only when its rc search cannot hit; the reads whose rc search
-    // finds nothing without one get it in the forward pass below.  It pays for long reads
-    // (config 5's 250 bp: k_widths 17.0 -> 15.7 ms); for 100 bp reads the second width
-    // launch costs more than the rows it saves (5.25 -> 5.68 ms), so by default reads of
-    // 200 bases or more (HSA_LAZY=0 / 1 forbids / forces it)
+    // finds nothing without one get it in the forward pass below.  One launch computes both
+    // kinds of row (k_widths_lazy), so it saves the rows of the reads whose rc strand can
+    // hit without a second width launch.  By default for ungapped searches of reads of 100
+    // bases or more (config 2, three handles: 66.7-68.1 against 64.9-67.6 M reads/s eager in
+    // seven pairs, k_widths' read requests 216 -> 189 M per launch) and for gapped ones from
+    // 200 bases: config 3's 100 bp reads lose 3 % to the forward pass, a second k_search
+    // launch with a long gapped tail (profiles/lazyrows_ab.log).  HSA_LAZY=0 / 1 forbids /
+    // forces it
     const char *le = getenv("HSA_LAZY");
-    const bool lazy = !split && !lk.n_dev && first && n > 0 && (le ? atoi(le) != 0 : io.max_len >= 200);
+    const int lazy_min = P.gaps ? HSA_LAZY_MIN_LEN_GAPPED : HSA_LAZY_MIN_LEN;
+    const bool lazy = !split && !lk.n_dev && first && n > 0 && (le ? atoi(le) != 0 : io.max_len >= lazy_min);
     unsigned long long *d_fwd_n = nullptr;
-    int32_t *d_list2 = nullptr;
-    unsigned long long *d_n2 = nullptr;
     if (lazy) {
-        // [count, count2 | forward-pass list (n) | list2 (n)]
-        if ((rc = hsa_grow(&ix->d_fwd, &ix->d_fwd_cap, 512 + 12 * (size_t)n))) return rc;
+        // [count | forward-pass list (n) | rmap (n)]
+        if ((rc = hsa_grow(&ix->d_fwd, &ix->d_fwd_cap, 512 + 8 * (size_t)n))) return rc;
         d_fwd_n = (unsigned long long *)ix->d_fwd;
-        d_n2 = d_fwd_n + 1;
         HSA_HIP(hipMemsetAsync(d_fwd_n, 0, 16, st));
         A.fwd_n = d_fwd_n;
         A.fwd_list = (int32_t *)((char *)ix->d_fwd + 128);
-        d_list2 = A.fwd_list + ((size_t)n + 31) / 32 * 32;
-        A.rmap = d_list2 + ((size_t)n + 31) / 32 * 32;
+        A.rmap = A.fwd_list + ((size_t)n + 31) / 32 * 32;
     }
     if (lazy) {
         const unsigned rblocks = (unsigned)(((size_t)n + BLOCK - 1) / BLOCK);
-        if (P.wide) {
-            hipLaunchKernelGGL((k_widths_reads<uint16_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, A, 1u, d_list2, d_n2);
-            hipLaunchKernelGGL((k_widths_reads<uint16_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, A, 3u, d_list2, d_n2);
-        } else if (P.snib) {
-            hipLaunchKernelGGL((k_widths_reads<uint8_t, IT, true>), dim3(rblocks), dim3(BLOCK), 0, st, A, 1u, d_list2, d_n2);
-            hipLaunchKernelGGL((k_widths_reads<uint8_t, IT, true>), dim3(rblocks), dim3(BLOCK), 0, st, A, 3u, d_list2, d_n2);
-        } else {
-            hipLaunchKernelGGL((k_widths_reads<uint8_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, A, 1u, d_list2, d_n2);
-            hipLaunchKernelGGL((k_widths_reads<uint8_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, A, 3u, d_list2, d_n2);
-        }
+        if (P.wide) hipLaunchKernelGGL((k_widths_lazy<uint16_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, A);
+        else if (P.snib) hipLaunchKernelGGL((k_widths_lazy<uint8_t, IT, true>), dim3(rblocks), dim3(BLOCK), 0, st, A);
+        else hipLaunchKernelGGL((k_widths_lazy<uint8_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, A);
     } else {
         size_t wblocks = ((size_t)n * 2 + BLOCK - 1) / BLOCK;
         if (wblocks < 1) wblocks = 1;
@@ -691,9 +685,9 @@ static int launch_pass(hsa_index *ix, const LaunchPlan &P0, SearchScratch &S, co
         F.job_list = A.fwd_list; F.n_dev = d_fwd_n; F.qctr = CTR_Q_FWD; F.fwd_only = 1;
         F.fwd_list = nullptr; F.fwd_n = nullptr; F.wkey = nullptr; F.perm = nullptr; F.rmap = nullptr;
         const unsigned rblocks = (unsigned)(((size_t)n + BLOCK - 1) / BLOCK);
-        if (P.wide) hipLaunchKernelGGL((k_widths_reads<uint16_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, F, 2u, d_list2, d_n2);
-        else if (P.snib) hipLaunchKernelGGL((k_widths_reads<uint8_t, IT, true>), dim3(rblocks), dim3(BLOCK), 0, st, F, 2u, d_list2, d_n2);
-        else hipLaunchKernelGGL((k_widths_reads<uint8_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, F, 2u, d_list2, d_n2);
+        if (P.wide) hipLaunchKernelGGL((k_widths_fwd<uint16_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, F);
+        else if (P.snib) hipLaunchKernelGGL((k_widths_fwd<uint8_t, IT, true>), dim3(rblocks), dim3(BLOCK), 0, st, F);
+        else hipLaunchKernelGGL((k_widths_fwd<uint8_t, IT>), dim3(rblocks), dim3(BLOCK), 0, st, F);
         HSA_HIP(hipGetLastError());
         launch_search<IT>(P, F, st);
         HSA_HIP(hipGetLastError());

@@ -25,8 +25,9 @@ import statistics
 import sys
 
 
-STEP_KERNELS = ("k_widths", "k_widths_reads", "k_search", "k_seed_prep", "k_widths_import", "k_widths_export",
-                "k_sp_prep", "k_pf_rows", "k_pf_seeds", "k_pf_anchors", "k_splice")
+# (k_widths_reads: the two-launch lazy widths of builds before k_widths_lazy)
+STEP_KERNELS = ("k_widths", "k_widths_lazy", "k_widths_fwd", "k_widths_reads", "k_search", "k_seed_prep",
+                "k_widths_import", "k_widths_export", "k_sp_prep", "k_pf_rows", "k_pf_seeds", "k_pf_anchors", "k_splice")
 
 
 def counters(d, kernel, every=False):
@@ -98,7 +99,7 @@ def main():
     else:
         # one step = k_widths + k_search launches: per-kernel medians, summed
         out["per_kernel"] = {}
-    for k in (() if launches else ("k_widths", "k_widths_reads", "k_search")):
+    for k in (() if launches else ("k_widths", "k_widths_lazy", "k_widths_fwd", "k_widths_reads", "k_search")):
         f, dur = counters(os.path.join(src, "pmc_fetch"), k)
         w, _ = counters(os.path.join(src, "pmc_write"), k)
         if not f:
@@ -121,6 +122,14 @@ def main():
         tcc, _ = counters(os.path.join(src, "pmc_tcc"), "k_search")
         h, m = med(tcc, "TCC_HIT_sum"), med(tcc, "TCC_MISS_sum")
         out["tcc"] = {"hit_rate": h / (h + m), "ea_rdreq": med(tcc, "TCC_EA0_RDREQ_sum")}
+        # every step kernel's memory read requests and duration per full-size launch
+        out["tcc"]["per_kernel"] = {}
+        for k in ("k_widths", "k_widths_lazy", "k_widths_fwd", "k_widths_reads", "k_search"):
+            t, dur = counters(os.path.join(src, "pmc_tcc"), k)
+            if t and med(t, "TCC_EA0_RDREQ_sum") > 0:
+                out["tcc"]["per_kernel"][k] = {"ea_rdreq": med(t, "TCC_EA0_RDREQ_sum"), "l2_hits": med(t, "TCC_HIT_sum"),
+                                               "l2_misses": med(t, "TCC_MISS_sum"), "launches": len(t),
+                                               "ms_median_pmc_pass": statistics.median(dur.values())}
     json.dump(out, open(dst, "w"), indent=1)
     print(json.dumps(out, indent=1))
 
