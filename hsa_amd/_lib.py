@@ -38,7 +38,7 @@ EXPORTS = [  # every symbol include/hsa_gpu.h and include/hsa_bwtaln.h declare
     "hsa_sa_position_batch64", "hsa_sa_position_device64", "hsa_psi_minus_batch64", "hsa_hit_positions_device64",
     "hsa_index_set_text64_device", "hsa_refine_rows_device64", "hsa_choose_hits_device64",
     "hsa_choose_timing", "hsa_choose_launch_times", "hsa_sam_lines_device64", "hsa_sam_timing",
-    "hsa_sam_launch_times",
+    "hsa_sam_launch_times", "hsa_index_levels",
 ]
 SP_RES_WORDS = 20  # hsa_splice_match_batch's per-read answer (include/hsa_gpu.h)
 ALN64_WORDS = 14   # hsa_aln64_t (include/hsa_gpu.h)
@@ -273,6 +273,8 @@ def lib():
     L.hsa_index_bytes.restype = C.c_size_t
     L.hsa_index_bytes.argtypes = [vp]
     L.hsa_index_trie.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "hsa_index_levels"):              # (older A/B builds lack it)
+        L.hsa_index_levels.argtypes = [vp, C.c_void_p, C.c_void_p]
     L.hsa_index_clone.argtypes = [vp, C.POINTER(vp)]
     L.hsa_index_stream.restype = vp
     L.hsa_index_stream.argtypes = [vp]
@@ -745,6 +747,12 @@ class GpuIndex:
         d, sd, b = C.c_uint32(), C.c_uint32(), C.c_size_t()
         check(lib().hsa_index_trie(self.h, C.byref(d), C.byref(sd), C.byref(b)))
         return int(d.value), int(sd.value), int(b.value)
+
+    def levels(self):
+        """(level of the implicit root levels' table, its strings that do not occur)."""
+        lv, ab = C.c_uint32(), C.c_uint32()
+        check(lib().hsa_index_levels(self.h, C.byref(lv), C.byref(ab)))
+        return int(lv.value), int(ab.value)
 
     def occ4(self, d, pos):
         pos = np.ascontiguousarray(pos, np.uint32)

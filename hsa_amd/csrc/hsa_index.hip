@@ -361,9 +361,13 @@ static int build_tries_t(hsa_index *ix, RD rev, IT T, const IT *C)
 // The implicit root levels of hsa_trie.h: level after level of the prepend trie on the
 // forward BWT, each from the one before, until a level is not complete (some string of
 // that length does not occur), HSA_SDEPTH levels are built (default HSA_SDEPTH_DEFAULT, at
-// most HSA_SDEPTH_MAX; 0 = none) or the next level does not fit in device memory.  Only the
-// deepest complete level is kept.  Like the width trie it only saves rank steps: none
-// (sdepth 0) is not an error.
+// most HSA_SDEPTH_MAX; 0 = none) or the next level does not fit in device memory.  The
+// complete levels are carried as node numbers; one level is kept as the table.  With
+// HSA_SPARTIAL (default 1; 0: the table stays on the deepest complete level) that is the
+// level after the last complete one when it is only incomplete -- strings that do not
+// occur, stored with their empty intervals -- or when HSA_SDEPTH stopped the complete
+// levels before it; a level with an unusable interval is dropped.  Like the width trie
+// the levels only save rank steps: none (sdepth 0) is not an error.
 static int build_search_levels(hsa_index *ix)
 {
     uint32_t D = HSA_SDEPTH_DEFAULT;
@@ -371,47 +375,70 @@ static int build_search_levels(hsa_index *ix)
         const int v = atoi(e);
         D = v < 0 ? 0u : (uint32_t)v > HSA_SDEPTH_MAX ? HSA_SDEPTH_MAX : (uint32_t)v;
     }
-    ix->sdepth = 0;
+    bool partial = true;
+    if (const char *e = getenv("HSA_SPARTIAL")) partial = atoi(e) != 0;
+    ix->sdepth = ix->slevel = ix->sabsent = 0;
     ix->d_trie_s = nullptr;
     if (D == 0) return 0;
     TrieC<uint32_t> Cv;
     for (int c = 0; c < 4; ++c) Cv.v[c] = ix->C[c];
     const RankDir fwd{ix->blk[0], ix->isa0};
-    unsigned *d_bad = nullptr;
-    HSA_HIP(hipMalloc(&d_bad, 4));
-    HSA_HIP(hipMemsetAsync(d_bad, 0, 4, ix->stream));
+    unsigned *d_flags = nullptr;                 // {invalid, absent children} of the level being built
+    HSA_HIP(hipMalloc(&d_flags, 8));
     void *cur = nullptr;                         // level `depth`, complete (null: the root)
-    uint32_t depth = 0;
+    uint32_t depth = 0, level = 0, absent = 0;
     int rc = 0;
-    // a level of 4^d strings is complete only in a text of at least 4^d characters
-    while (depth < D && (1ull << (2 * (depth + 1))) <= (uint64_t)ix->T) {
+    // a level of 4^d strings is complete only in a text of at least 4^d characters (the
+    // same bound holds for the table's level)
+    while ((1ull << (2 * (depth + 1))) <= (uint64_t)ix->T) {
+        // level depth + 1: a complete level while HSA_SDEPTH allows one, else the table only
+        const bool may_complete = depth < D;
+        const bool may_table = partial && depth >= 1 && depth + 1 <= HSA_STAB_MAX;
+        if (!may_complete && !may_table) break;
         void *nxt = nullptr;
         if (hipMalloc(&nxt, (size_t)64 << (2 * depth)) != hipSuccess) {
             (void)hipGetLastError();
             if (getenv("HSA_VERBOSE")) fprintf(stderr, "[hsa] implicit levels: no device memory past level %u\n", depth);
             break;
         }
-        unsigned bad = 0;
+        unsigned flags[2] = {0, 0};
         const unsigned nb = (unsigned)(((1ull << (2 * depth)) + 255) / 256);
-        hipLaunchKernelGGL(k_trie_search_level, dim3(nb), dim3(256), 0, ix->stream, fwd, ix->T, Cv, depth, cur, nxt, d_bad);
+        if (hipMemsetAsync(d_flags, 0, 8, ix->stream) == hipSuccess)
+            hipLaunchKernelGGL(k_trie_search_level, dim3(nb), dim3(256), 0, ix->stream, fwd, ix->T, Cv, depth, cur, nxt, d_flags);
         if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, ix->stream) != hipSuccess ||
+            hipMemcpyAsync(flags, d_flags, 8, hipMemcpyDeviceToHost, ix->stream) != hipSuccess ||
             hipStreamSynchronize(ix->stream) != hipSuccess) {
             hsa_set_error("implicit levels: building level %u failed", depth + 1);
             (void)hipFree(nxt);
             rc = HSA_E_HIP;
             break;
         }
-        if (bad) { (void)hipFree(nxt); break; }  // level depth + 1 is not complete
+        if (flags[0]) { (void)hipFree(nxt); break; }     // level depth + 1 is invalid: dropped
+        if (flags[1] || !may_complete) {
+            // not complete, or past HSA_SDEPTH: the table's level, or dropped
+            if (may_table) {
+                (void)hipFree(cur);
+                cur = nxt;
+                level = depth + 1;
+                absent = flags[1];
+            } else {
+                (void)hipFree(nxt);
+            }
+            break;
+        }
         (void)hipFree(cur);
         cur = nxt;
         ++depth;
     }
-    (void)hipFree(d_bad);
+    (void)hipFree(d_flags);
     if (rc) { (void)hipFree(cur); return rc; }
     ix->d_trie_s = cur;
     ix->sdepth = depth;
-    if (getenv("HSA_VERBOSE")) fprintf(stderr, "[hsa] implicit levels: %u (%zu bytes)\n", depth, depth ? (size_t)16 << (2 * depth) : (size_t)0);
+    ix->slevel = level ? level : depth;
+    ix->sabsent = absent;
+    if (getenv("HSA_VERBOSE"))
+        fprintf(stderr, "[hsa] implicit levels: %u complete, table on level %u (%u absent, %zu bytes)\n", depth, ix->slevel,
+                absent, ix->slevel ? (size_t)16 << (2 * ix->slevel) : (size_t)0);
     return 0;
 }
 
@@ -555,6 +582,7 @@ extern "C" int hsa_index_clone(hsa_index_t *src, hsa_index_t **out)
     ix->trie_depth = root->trie_depth;
     ix->trie_wide = root->trie_wide; ix->trie_bytes = root->trie_bytes;
     ix->d_trie_s = root->d_trie_s; ix->sdepth = root->sdepth;
+    ix->slevel = root->slevel; ix->sabsent = root->sabsent;
     ix->parent = root;
     __atomic_add_fetch(&root->n_clones, 1, __ATOMIC_ACQ_REL);
     *out = ix;
@@ -642,6 +670,12 @@ extern "C" int hsa_index_trie(const hsa_index_t *ix, uint32_t *depth, uint32_t *
     if (depth) *depth = ix->trie_depth;
     if (sdepth) *sdepth = ix->sdepth;          // k_search's implicit root levels (hsa_trie.h)
     if (bytes) *bytes = ix->trie_bytes;
+    return 0;
+}
+extern "C" int hsa_index_levels(const hsa_index_t *ix, uint32_t *table_level, uint32_t *absent)
+{
+    if (table_level) *table_level = ix->slevel;
+    if (absent) *absent = ix->sabsent;
     return 0;
 }
 extern "C" int hsa_index_device(const hsa_index_t *ix) { return ix->device; }

@@ -130,11 +130,14 @@ struct hsa_index {
     uint32_t trie_depth = 0;
     bool trie_wide = false;
     size_t trie_bytes = 0;
-    // the implicit root levels of k_search (hsa_trie.h): level sdepth of the prepend
-    // trie on the forward BWT, one 64-byte sector per level-(sdepth - 1) node; 0 = none
-    // (a wide index has none)
+    // the implicit root levels of k_search (hsa_trie.h): sdepth complete, load-free levels
+    // of the prepend trie on the forward BWT and the table of level slevel (sdepth, or
+    // sdepth + 1 with sabsent strings that do not occur), one 64-byte sector per node of
+    // the level above it; 0 = none (a wide index has none)
     void *d_trie_s = nullptr;
     uint32_t sdepth = 0;
+    uint32_t slevel = 0;
+    uint32_t sabsent = 0;
     unsigned char staged[1280];         // last regime block copied to d_in (skip identical re-copies)
     int staged_valid = 0;
     bool staged_mmb = false;            // staged regimes: bucket == n_mm (see mm_buckets)

@@ -150,9 +150,10 @@ struct SearchArgs {
                                    // searches ended [7] owners answered by their helpers [8] sub-searches'
                                    // rank queries [9] ready-queue tail
     // the implicit root levels (hsa_trie.h; ungapped 32-bit kernels with 8/16-bit rows, not
-    // the HUGE pass): level sdc of the index's prepend trie, one 64-byte sector per
-    // level-(sdc - 1) node; sdc 0: none.  (Last in the struct: the gapped kernels' argument
-    // offsets stay what they were.)
+    // the HUGE pass): level sdc of the index's prepend trie, the table's level, one 64-byte
+    // sector per level-(sdc - 1) node; every level above it is complete, level sdc itself
+    // may hold strings that do not occur (k > l); sdc 0: none.  (Last in the struct: the
+    // gapped kernels' argument offsets stay what they were.)
     const void *stw;
     uint32_t sdc;
 };
@@ -921,6 +922,7 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
     // which every string occurs nothing reads its interval: a read longer than sdc keeps
     // its entries of fewer than sdc characters as trie node numbers (Ent::x; y and z
     // unused) and expands them without a rank step.  The root {0, T, 0} is node 0 as it is.
+    // Level sdc, the table's, need not be complete: its entries carry their intervals.
     constexpr bool IMP = !GAPS && !HUGE && sizeof(IT) == 4 && !WFmt<WT>::NIB;
 #ifdef HSA_DIAG
     if (threadIdx.x == 0 && blockIdx.x < 8192) {
@@ -1810,12 +1812,17 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
         if (IMP && req == 3) {
             // the exact tail leaves the implicit levels: the level-sdc node's interval.  The
             // write-back guard below tests which fields of the entry the tail started from
-            // are zero.  Of a string on a complete level none is (the builder checks
+            // are zero.  That entry has fewer than sdc characters, so it is on a complete
+            // level, and of a string on a complete level none is (the builder checks
             // k >= 1 and rev_k >= 1, and l >= k, rev_l >= rev_k), so a node entry gets
             // non-zero fields here; the root keeps its own, {0, T, 0}.
+            // Level sdc itself may lack the string (k > l in the table): the tail ends as
+            // bwt_match_exact does on an empty interval (2BWT-Interface.c:378-382), without a
+            // hit; the failing step's two queries are counted by the appending loop.
             ik = oa[0]; il = ob[0]; aux = srk[0] + (il - ik);
             if (M_I(e.w) != C_LEN(ctl)) e.x = e.y = e.z = 1u;
             --pos;
+            if (ik > il) SET_PH(ctl, PH_POP);
         } else if (F::NIB && req == 1 && ph == PH_EXACT && cur_c > 3) {
             st_q -= 2u; st_b -= 1u + two;                                // not a step (2BWT-Interface.c:377)
             SET_PH(ctl, PH_POP);
@@ -1849,14 +1856,19 @@ __global__ void __launch_bounds__(NT, HSA_WAVES_SIMD) k_search(SearchArgs a)
             const int len = C_LEN(ctl);
             uint32_t ne = 0;                                             // children that occur
             if (IMP && req != 1) {
-                // implicit levels: all four children occur; they are the nodes 4 p + c, or
-                // (req 2) the table's level-sdc intervals, already in oa, ob, srk.  The
-                // reference issues the step's two queries.
+                // implicit levels: the children are the nodes 4 p + c, all four of which
+                // occur (req 4), or the table's level-sdc intervals, already in oa, ob, srk
+                // (req 2), of which a string that does not occur has k > l as a rank step
+                // gives it.  The reference issues the step's two queries.
+                ne = 0xFu;
                 if (req == 4) {
 #pragma unroll
                     for (int c = 0; c < 4; ++c) { oa[c] = ek * 4u + (IT)c; ob[c] = 0; srk[c] = 0; }
+                } else {
+                    ne = 0;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) ne |= (oa[c] <= ob[c] ? 1u : 0u) << c;
                 }
-                ne = 0xFu;
                 st_q += 2u;
             } else {
                 IT oc = 0;

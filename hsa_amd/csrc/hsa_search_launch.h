@@ -433,7 +433,7 @@ static int pass_args(hsa_index *ix, const LaunchPlan &P, SearchScratch &S, const
     A.split = 0; A.sp_n = nullptr; A.sp_off = nullptr; A.sp_q = nullptr; A.sp_p = nullptr;
     A.ktd = trie_levels(ix, sizeof(IT) == 8);
     A.ktw = A.ktd ? ix->d_trie_w : nullptr;
-    A.sdc = sizeof(IT) == 4 ? ix->sdepth : 0u;
+    A.sdc = sizeof(IT) == 4 ? ix->slevel : 0u;   // the table's level (sdepth or sdepth + 1)
     A.stw = A.sdc ? ix->d_trie_s : nullptr;
     A.wkey = nullptr; A.perm = nullptr; A.okey = 0;
     A.fwd_list = nullptr; A.fwd_n = nullptr; A.fwd_only = 0; A.rmap = nullptr;

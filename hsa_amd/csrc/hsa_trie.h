@@ -31,12 +31,22 @@
 // of which every string occurs in the text (a COMPLETE level: all of a node's four
 // children exist) an ungapped search reads nothing of an entry's interval until it
 // leaves the level -- pruning works on the width rows and the entry's meta word -- so
-// k_search carries the node number instead and only level Dc is kept, Dc being the
-// deepest complete level (at most HSA_SDEPTH, HSA_SDEPTH_MAX): {k, l, rev_k} per node, the
-// four children of one level-(Dc - 1) node in one 64-byte sector, words [0,4) their k,
-// [4,8) their l, [8,12) their rev_k.  16 B x 4^Dc.  The levels are the kernel's own
-// step arithmetic applied to the previous level, so the values are bit-identical to
-// the rank steps'.
+// k_search carries the node number instead, up to level Dc, the deepest complete level
+// (at most HSA_SDEPTH, HSA_SDEPTH_MAX), and one level is kept as a table: {k, l, rev_k}
+// per node, the four children of one node of the level above in one 64-byte sector,
+// words [0,4) their k, [4,8) their l, [8,12) their rev_k.  The levels are the kernel's
+// own step arithmetic applied to the previous level, so the values are bit-identical
+// to the rank steps'.
+//
+// The table level is Dc + 1 (16 B x 4^(Dc+1), at most level HSA_STAB_MAX), the first
+// level that need not be complete.  Completeness is needed only of the levels whose
+// entries are node numbers without an interval; the table stores every node's interval,
+// and a string that does not occur has there the empty interval (k = l + 1) the rank
+// step itself computes for it, so the kernel tests k <= l of a table child as it does
+// of a rank step's.  A step from level Dc - 1 to Dc then takes no load, and a step from
+// Dc to Dc + 1 one table sector in place of two rank blocks.  The level is dropped (the
+// table stays on level Dc) when a string of it that occurs has an unusable interval,
+// when 4^(Dc+1) > T, when it does not fit in device memory, or with HSA_SPARTIAL=0.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -100,8 +110,9 @@ __global__ void __launch_bounds__(256) k_trie_width_level(RD rev, IT T, TrieC<IT
 // ---------------------------------------------------------------- implicit root levels
 #define HSA_SDEPTH_MAX 13u          // 16 B x 4^13 = 1 GiB
 #define HSA_SDEPTH_DEFAULT 13u
+#define HSA_STAB_MAX 14u            // the table's level: 16 B x 4^14 = 4 GiB
 
-// the level-Dc sector of level-(Dc - 1) node p: its four children's k, l, rev_k
+// the table sector of node p of the level above the table's: its four children's k, l, rev_k
 __device__ __forceinline__ void trie_s_load4(const void *t, uint32_t p, uint32_t k[4], uint32_t l[4], uint32_t rk[4])
 {
     const uint4 *s = reinterpret_cast<const uint4 *>(t) + (size_t)p * 4;
@@ -111,7 +122,7 @@ __device__ __forceinline__ void trie_s_load4(const void *t, uint32_t p, uint32_t
     rk[0] = vr.x; rk[1] = vr.y; rk[2] = vr.z; rk[3] = vr.w;
 }
 
-// one level-Dc node n (child n & 3 of node n >> 2)
+// one node n of the table's level (child n & 3 of node n >> 2)
 __device__ __forceinline__ void trie_s_load1(const void *t, uint32_t n, uint32_t &k, uint32_t &l, uint32_t &rk)
 {
     const uint32_t *s = reinterpret_cast<const uint32_t *>(t) + (size_t)(n >> 2) * 16 + (n & 3u);
@@ -119,36 +130,46 @@ __device__ __forceinline__ void trie_s_load1(const void *t, uint32_t n, uint32_t
 }
 
 // Level d (src; the root when d == 0) -> level d + 1 (dst, 4^d sectors): k_search's
-// expansion arithmetic (2BWT-Interface.c:235-272) on the forward BWT.  *bad is raised
-// when level d + 1 is not complete: a child that does not occur, or one with a zero k or
-// rev_k (k_search's exact tail relies on both being non-zero below the root), or an
-// interval past the text.  The caller launches it only on a complete level d, so every
-// rank position is inside the text.
+// expansion arithmetic (2BWT-Interface.c:235-272) on the forward BWT.  Two defects of
+// level d + 1 are reported apart.  flags[0] is raised when the level is INVALID: a child
+// that occurs has a zero k or rev_k (k_search's exact tail relies on both being non-zero
+// below the root) or an interval past the text.  flags[1] counts the ABSENT children
+// (k > l; a per-block sum, one atomic per block); they are stored with the values the
+// arithmetic gives them, as every other child.  The caller launches it only on a complete
+// level d, so every rank position is inside the text.
 static __global__ void __launch_bounds__(256) k_trie_search_level(RankDir fwd, uint32_t T, TrieC<uint32_t> Cg, uint32_t d,
                                                                   const void *__restrict__ src, void *__restrict__ dst,
-                                                                  unsigned *bad)
+                                                                  unsigned *flags)
 {
+    __shared__ unsigned s_absent;
+    if (threadIdx.x == 0) s_absent = 0u;
+    __syncthreads();
     const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= (1ull << (2u * d))) return;
-    uint32_t k = 0, l = T, rk = 0;
-    if (d > 0) trie_s_load1(src, (uint32_t)p, k, l, rk);
-    uint32_t oa[4], ob[4], sr[4];
-    occ_pair(fwd, k, l + 1u, oa, ob);
-    const uint32_t erl = rk + (l - k);
-    uint32_t oc = 0;
-    bool ok = true;
-    for (int c = 3; c >= 0; --c) {
-        const uint32_t n = ob[c] - oa[c];
-        oa[c] = Cg.v[c] + oa[c] + 1u;
-        ob[c] = Cg.v[c] + ob[c];
-        sr[c] = (erl - oc) - (ob[c] - oa[c]);
-        oc += n;
-        ok = ok && oa[c] >= 1u && oa[c] <= ob[c] && ob[c] <= T && sr[c] >= 1u;
+    if (p < (1ull << (2u * d))) {
+        uint32_t k = 0, l = T, rk = 0;
+        if (d > 0) trie_s_load1(src, (uint32_t)p, k, l, rk);
+        uint32_t oa[4], ob[4], sr[4];
+        occ_pair(fwd, k, l + 1u, oa, ob);
+        const uint32_t erl = rk + (l - k);
+        uint32_t oc = 0, na = 0;
+        bool ok = true;
+        for (int c = 3; c >= 0; --c) {
+            const uint32_t n = ob[c] - oa[c];
+            oa[c] = Cg.v[c] + oa[c] + 1u;
+            ob[c] = Cg.v[c] + ob[c];
+            sr[c] = (erl - oc) - (ob[c] - oa[c]);
+            oc += n;
+            if (oa[c] > ob[c]) ++na;
+            else ok = ok && oa[c] >= 1u && ob[c] <= T && sr[c] >= 1u;
+        }
+        uint4 *s = reinterpret_cast<uint4 *>(dst) + p * 4;
+        s[0] = make_uint4(oa[0], oa[1], oa[2], oa[3]);
+        s[1] = make_uint4(ob[0], ob[1], ob[2], ob[3]);
+        s[2] = make_uint4(sr[0], sr[1], sr[2], sr[3]);
+        s[3] = make_uint4(0u, 0u, 0u, 0u);
+        if (!ok) flags[0] = 1u;
+        if (na) atomicAdd(&s_absent, na);
     }
-    uint4 *s = reinterpret_cast<uint4 *>(dst) + p * 4;
-    s[0] = make_uint4(oa[0], oa[1], oa[2], oa[3]);
-    s[1] = make_uint4(ob[0], ob[1], ob[2], ob[3]);
-    s[2] = make_uint4(sr[0], sr[1], sr[2], sr[3]);
-    s[3] = make_uint4(0u, 0u, 0u, 0u);
-    if (!ok) *bad = 1u;
+    __syncthreads();
+    if (threadIdx.x == 0 && s_absent) atomicAdd(&flags[1], s_absent);
 }

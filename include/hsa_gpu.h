@@ -108,8 +108,14 @@ int  hsa_index_device(const hsa_index_t *ix);
  * are counted in d_counters[10].  *sdepth: the implicit root levels of the ungapped
  * k_search -- the deepest level of which every string occurs in the text, at most
  * HSA_SDEPTH at creation (default and most 13; 0: none, as for a 64-bit index); its
- * table, 16 B x 4^sdepth, is not part of *bytes. */
+ * table (hsa_index_levels) is not part of *bytes. */
 int  hsa_index_trie(const hsa_index_t *ix, uint32_t *depth, uint32_t *sdepth, size_t *bytes);
+/* The level the implicit root levels' table holds, 16 B x 4^*table_level of device memory
+ * (0: none): sdepth + 1, the first level that need not be complete (at most 14; *absent of
+ * its strings do not occur in the text and are stored with their empty intervals), or
+ * sdepth when that level is unusable, does not fit, or HSA_SPARTIAL=0 was set at creation
+ * (*absent 0).  A clone reports its parent's values. */
+int  hsa_index_levels(const hsa_index_t *ix, uint32_t *table_level, uint32_t *absent);
 /* A second handle on the same resident index, for passes that run concurrently: the
  * clone shares src's read-only device arrays (rank blocks, wrap tables, trie, SA) and
  * has its own stream, events and search scratch, so hsa_search_device on
