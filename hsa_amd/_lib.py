@@ -38,7 +38,8 @@ EXPORTS = [  # every symbol include/hsa_gpu.h and include/hsa_bwtaln.h declare
     "hsa_sa_position_batch64", "hsa_sa_position_device64", "hsa_psi_minus_batch64", "hsa_hit_positions_device64",
     "hsa_index_set_text64_device", "hsa_refine_rows_device64", "hsa_choose_hits_device64",
     "hsa_choose_timing", "hsa_choose_launch_times", "hsa_sam_lines_device64", "hsa_sam_timing",
-    "hsa_sam_launch_times", "hsa_index_levels",
+    "hsa_sam_launch_times", "hsa_index_levels", "hsa_reads_device", "hsa_reads_timing",
+    "hsa_reads_launch_times",
 ]
 SP_RES_WORDS = 20  # hsa_splice_match_batch's per-read answer (include/hsa_gpu.h)
 ALN64_WORDS = 14   # hsa_aln64_t (include/hsa_gpu.h)
@@ -53,6 +54,15 @@ CHOOSE_NONE, CHOOSE_UNIQUE, CHOOSE_REPEAT = range(3)
 # hsa_sam_lines_device64: per-read status, the longest line a batch may declare
 HSA_SAM_OK, HSA_SAM_NOHIT, HSA_SAM_ROWS, HSA_SAM_REFINE, HSA_SAM_INPUT = range(5)
 HSA_SAM_MAX_LINE = 61440
+# hsa_reads_device: per-record status, words per record row, the longest read, the bytes of
+# the input per block of the newline passes, the counters
+HSA_RD_SEARCHED, HSA_RD_NDROP, HSA_RD_POLYAT = range(3)
+RD_ROW_WORDS = 4
+HSA_RD_MAX_LEN = 65535
+HSA_RD_TILE = 4096
+RD_COUNTERS = ("seen", "loaded", "jobs_wanted", "jobs_written", "code_wanted", "code_written", "name_wanted",
+               "name_written", "qual_wanted", "qual_written", "consumed", "bad_record", "bad_offset", "max_loaded",
+               "max_kept", "threshold")
 
 
 class HsaError(RuntimeError):
@@ -181,6 +191,19 @@ class SamBatch64(C.Structure):
                 ("d_chr_names", C.c_void_p), ("d_chr_off", C.c_void_p), ("n_chr", C.c_uint32), ("flag", C.c_uint32),
                 ("max_top2", C.c_int32), ("comp_read", C.c_int32), ("max_line", C.c_uint32), ("d_line_off", C.c_void_p),
                 ("d_out", C.c_void_p), ("out_cap", C.c_uint64), ("d_line_stat", C.c_void_p), ("d_counters", C.c_void_p)]
+
+
+class ReadsBatch(C.Structure):
+    """hsa_reads_batch_t (include/hsa_gpu.h): the bytes of a FASTQ chunk in; the search
+    batch (jobs, codes), the names and qualities in hsa_sam_lines_device64's layout, a row
+    per record and the counters out, all device pointers."""
+    _fields_ = [("d_in", C.c_void_p), ("n_in", C.c_uint64), ("at_eof", C.c_int32), ("max_records", C.c_uint32),
+                ("max_diff", C.c_int32), ("d_maxdiff", C.c_void_p), ("n_maxdiff", C.c_uint32), ("len_floor", C.c_uint32),
+                ("seed_len", C.c_int32),
+                ("regime", C.c_int32), ("trim_qual", C.c_int32), ("mode", C.c_uint32), ("d_jobs", C.c_void_p),
+                ("job_cap", C.c_uint64), ("d_codes", C.c_void_p), ("code_cap", C.c_uint64), ("d_names", C.c_void_p),
+                ("name_cap", C.c_uint64), ("d_name_off", C.c_void_p), ("d_quals", C.c_void_p), ("qual_cap", C.c_uint64),
+                ("d_qual_off", C.c_void_p), ("d_rec", C.c_void_p), ("d_counters", C.c_void_p)]
 
 
 def log_n_table() -> np.ndarray:
@@ -341,6 +364,11 @@ def lib():
         L.hsa_sam_timing.argtypes = [C.c_int]
         L.hsa_sam_timing.restype = None
         L.hsa_sam_launch_times.argtypes = [vp, f32]
+    if hasattr(L, "hsa_reads_device"):              # (older A/B builds lack the FASTQ loader)
+        L.hsa_reads_device.argtypes = [vp, C.POINTER(ReadsBatch), vp]
+        L.hsa_reads_timing.argtypes = [C.c_int]
+        L.hsa_reads_timing.restype = None
+        L.hsa_reads_launch_times.argtypes = [vp, f32]
     if hasattr(L, "hsa_extend_batch"):
         L.hsa_extend_batch.argtypes = [vp, C.POINTER(Regime), C.c_int, vp, C.c_int, u8, i32, C.c_size_t, i32, i32,
                                        u32]
@@ -716,6 +744,25 @@ class GpuIndex:
         if not hasattr(lib(), "hsa_sam_lines_device64"):
             raise HsaError("this libhsa_gpu.so has no hsa_sam_lines_device64: rebuild it")
         check(lib().hsa_sam_lines_device64(getattr(self, "h", None), C.byref(batch), stream))
+
+    def reads_device(self, batch: "ReadsBatch", stream=None):
+        """hsa_reads_device: the bytes of a FASTQ chunk on the device to a search batch, the
+        names and qualities and a row per record (batch.d_jobs, d_codes, d_names, d_name_off,
+        d_quals, d_qual_off, d_rec, d_counters) on `stream` (a hipStream_t address; None: the
+        index's own); does not synchronise.  hsa_amd.reads.load_device drives it.  Without a
+        handle the library answers itself: HSA_E_NODEV where no GPU is visible."""
+        if not hasattr(lib(), "hsa_reads_device"):
+            raise HsaError("this libhsa_gpu.so has no hsa_reads_device: rebuild it")
+        check(lib().hsa_reads_device(getattr(self, "h", None), C.byref(batch), stream))
+
+    READS_LAUNCHES = ("count", "tile_scan", "lines", "record", "max_keep", "record_scan", "rows", "bytes")
+
+    def reads_launch_times(self) -> dict:
+        """hsa_reads_launch_times: ms per launch of this handle's last reads_device call made
+        after lib().hsa_reads_timing(1); waits for it."""
+        ms = np.zeros(len(self.READS_LAUNCHES), np.float32)
+        check(lib().hsa_reads_launch_times(self._handle(), ms))
+        return {k: float(v) for k, v in zip(self.READS_LAUNCHES, ms)}
 
     SAM_LAUNCHES = ("len", "scan", "write")
 

@@ -1,0 +1,574 @@
+"""FASTQ to SAM on the 64-bit path: `python -m hsa_amd.align [options] <prefix> <in.fq>`.
+
+open_index64 opens the index files `python -m hsa_amd.index_build` writes as a 64-bit
+GpuIndex; align_fastq drives, per batch of 0x186A0 reads (bwtaln.c:477), what
+bwa_aln_core does with it (bwtaln.c:452-531):
+
+  1. load the batch: hsa_reads_device (hsa_amd.reads.load_device) takes the canonical
+     records, hsa_amd.reads.parse_host the ones it refuses, one or a few at a time, and the
+     device loader goes on behind them;
+  2. search every kept read with the options as bwa_cal_sa_reg_gap sets them through
+     aux->opt (`mode &= ~BWA_MODE_GAPE`, bwtaln.c:261);
+  3. find the first read without a hit and search the reads after it again with the batch's
+     local options (bwtaln.c:363: aux->opt stays &local_opt for the rest of the batch);
+  4. choose, refine and write the SAM lines per part, the drand48 state chained through the
+     parts and the batches;
+  5. append the text to `out`.
+
+What the reference's loop does to its option block is kept over the batches: the GAPE bit
+stays cleared after the first batch (so only the first batch's local options have it), and
+opt->seed_len turns to 0x7fffffff for good at the first searched read, up to the switch, that
+is not longer than it (bwtaln.c:332 writes through aux->opt).
+
+Contract.  One line per read with a main-search hit, in read order, byte for byte
+bwa_print_sam1's (bwtse.c:698-799).  A read without one gets no line: the reference sends
+it to bwt_splice_match, for which the 64-bit path has no counterpart; such reads are counted
+and, with --unaligned FILE, written back out as FASTQ.  The text equals the reference's up
+to the first read whose line the reference prints from its splice path, because that read's
+drand48 draws are not seen here (tests/test_gpu_choose.py documents the condition).  No @SQ
+header unless --header is given; with it, "@SQ\\tSN:<name>\\tLN:<length>" per chromosome of the
+.ann file, the reference's format (bwt_print_sam_SQ, bwtse.c:826-834).
+
+Not built: quality trimming (-q), barcodes (-B), the Casava filter (-Y), Illumina-1.3
+qualities (-I), BAM input (-b, -0, -1, -2), colour space (-c): refused.  -t is accepted and
+ignored.  A read the choice counts as a zero-draw read (probability 2^-48 per read) stops the
+run with an error."""
+from __future__ import annotations
+
+import functools
+import gzip
+import sys
+
+import numpy as np
+
+from . import index_io, reads, sam
+from ._lib import (ALN64_WORDS, DRAND48_SEED0, HSA_RD_NDROP, HSA_RD_POLYAT, HSA_RD_SEARCHED, HSA_RF_MAX_LEN, HSA_RF_MD,
+                   JOB_DTYPE, RF_ROW_WORDS, ChooseBatch64, DeviceBatch, GapOpt, GpuIndex, HsaError, RefineBatch64, regime_of)
+
+HSA_DRAND48_SEED0 = DRAND48_SEED0
+BATCH_READS = 0x186A0            # bwtaln.c:477
+N_MULTI = 3                      # bwtaln.c:514
+MODE_GAPE, MODE_COMPREAD, MODE_LOGGAP, MODE_NONSTOP = 0x01, 0x02, 0x04, 0x10
+SEED_NONE = reads.SEED_NONE
+TABLE_LEN = HSA_RF_MAX_LEN + 1   # reads past it go through the host parser (and are not refined)
+ONES = 0xFFFFFFFFFFFFFFFF
+OPTSTRING = "n:o:e:i:d:l:k:cLR:m:t:NM:O:E:q:f:b012IYB:"       # bwtaln.c:539
+
+
+# ---------------------------------------------------------------- options
+def default_opts() -> dict:
+    """gap_init_opt (bwtaln.c:21-44); fnr as the float the reference stores."""
+    return GapOpt.default().as_dict()
+
+
+def _atoi(s: str) -> int:
+    """C's atoi: optional blanks and sign, then digits; 0 when there are none."""
+    s = s.lstrip(" \t\n\v\f\r")
+    k = 1 if s[:1] in ("+", "-") else 0
+    e = k
+    while e < len(s) and s[e].isascii() and s[e].isdigit():
+        e += 1
+    v = int(s[:e]) if e > k else 0
+    return ((v + 0x80000000) & 0xFFFFFFFF) - 0x80000000
+
+
+def _atof(s: str) -> float:
+    """C's atof on the longest decimal prefix; 0.0 when there is none."""
+    import re
+    m = re.match(r"[ \t\n\v\f\r]*[+-]?(\d+\.?\d*([eE][+-]?\d+)?|\.\d+([eE][+-]?\d+)?)", s)
+    return float(m.group(0)) if m else 0.0
+
+
+def parse_options(args):
+    """bwa_aln's option switch (bwtaln.c:539-575) over `args`: (the option dict, the
+    positional arguments, dict(header, unaligned, out)).  Options of what is not built raise
+    ValueError."""
+    import getopt
+    o = default_opts()
+    extra = dict(header=False, unaligned=None, out=None)
+    opte = -1
+    optlist, rest = getopt.gnu_getopt(list(args), OPTSTRING, ["header", "unaligned="])
+    plain = {"-o": "max_gapo", "-M": "s_mm", "-O": "s_gapo", "-E": "s_gape", "-d": "max_del_occ", "-i": "indel_end_skip",
+             "-l": "seed_len", "-k": "max_seed_diff", "-m": "max_entries", "-t": "n_threads", "-R": "max_top2"}
+    for k, v in optlist:
+        if k == "-n":
+            if "." in v:
+                o["fnr"], o["max_diff"] = float(np.float32(_atof(v))), -1
+            else:
+                o["max_diff"], o["fnr"] = _atoi(v), -1.0
+        elif k in plain:
+            o[plain[k]] = _atoi(v)
+        elif k == "-e":
+            opte = _atoi(v)
+        elif k == "-L":
+            o["mode"] |= MODE_LOGGAP
+        elif k == "-N":
+            o["mode"] |= MODE_NONSTOP
+            o["max_top2"] = 0x7FFFFFFF
+        elif k == "-q":
+            o["trim_qual"] = _atoi(v)
+        elif k == "-f":
+            extra["out"] = v
+        elif k == "--header":
+            extra["header"] = True
+        elif k == "--unaligned":
+            extra["unaligned"] = v
+        else:
+            raise ValueError(f"option {k} is not built (barcodes, Casava filter, Illumina-1.3 qualities, BAM, colour space)")
+    if opte > 0:
+        o["max_gape"] = opte
+        o["mode"] &= ~MODE_GAPE
+    if o["trim_qual"] != 0:
+        raise ValueError("quality trimming (-q) is not built")
+    return o, rest, extra
+
+
+# ---------------------------------------------------------------- the index
+def _msb_to_lsb(code, T):
+    """.bwt words (character j of a word at bits 31-2j .. 30-2j) to LSB-first words, the
+    codes past T cleared."""
+    x = np.ascontiguousarray(code, np.uint32).copy()
+    x = (x >> 16) | (x << 16)
+    x = ((x & 0xFF00FF00) >> 8) | ((x & 0x00FF00FF) << 8)
+    x = ((x & 0xF0F0F0F0) >> 4) | ((x & 0x0F0F0F0F) << 4)
+    x = (((x & 0xCCCCCCCC) >> 2) | ((x & 0x33333333) << 2)).astype(np.uint32)
+    if T % 16:
+        x[-1] &= np.uint32((1 << (2 * (T % 16))) - 1)
+    return x
+
+
+def read_chromosomes(prefix: str):
+    """(names, lengths) by chrID from prefix.index.ann; a length is the span of the
+    chromosome's blocks."""
+    with open(prefix + ".index.ann") as f:
+        ls = f.read().split("\n")
+    n_chr = int(ls[0].split()[1])
+    names = [ls[1 + k].split()[1] for k in range(n_chr)]
+    blocks = index_io.read_blocks(prefix).astype(np.int64)
+    lens = []
+    for c in range(n_chr):
+        b = blocks[blocks[:, 0] == c]
+        lens.append(int(b[:, 2].max() - b[:, 1].min() + 1) if len(b) else 0)
+    return names, lens
+
+
+def open_index64(prefix: str, device: int = 0):
+    """(GpuIndex, chromosome names) from the index files of `prefix` (prefix.index.*): a
+    64-bit index (hsa_index_create_device64) with both BWTs, the SA samples (as they are for
+    the 32-bit calls, and widened to u64 for the 64-bit ones) with the block table, and the
+    packed text."""
+    import torch
+    fwd, rev = index_io.read_index(prefix)
+    up = lambda b: torch.from_numpy(np.concatenate([_msb_to_lsb(b.code, b.T), np.zeros(8, np.uint32)]).view(np.int32)).cuda(device)
+    d_f, d_r = up(fwd), up(rev)
+    torch.cuda.synchronize()
+    gi = GpuIndex.from_device_codes64(fwd.T, fwd.isa0, np.asarray(fwd.C, np.uint64), d_f.data_ptr(), rev.T, rev.isa0,
+                                      np.asarray(rev.C, np.uint64), d_r.data_ptr(), device=device)
+    sa, blocks = index_io.read_sa(prefix), index_io.read_blocks(prefix)
+    gi.set_sa(sa, blocks)
+    vals = np.asarray(sa.values, np.uint32)
+    gi.set_sa64(np.where(vals == np.uint32(0xFFFFFFFF), np.uint64(ONES), vals.astype(np.uint64)), sa.interval,
+                blocks.astype(np.uint64))
+    gi.set_text(*index_io.read_packed_dna(prefix))
+    return gi, read_chromosomes(prefix)[0]
+
+
+# ---------------------------------------------------------------- the option switch's side effects
+def post_switch_skips(lens, n_n, polyat, first, maxdiff_of, thr0):
+    """The records from `first` on (the one after the first read without a hit) that
+    bwa_cal_sa_reg_gap skips at bwtaln.c:314-317.  After the switch aux->opt is &local_opt, so
+    :331 writes each searched read's max_diff into local_opt.max_diff, the value :316 compares
+    the next read's N count with: the threshold is the max_diff of the latest searched read,
+    thr0 (the batch's) until there is one.  A skipped read and a poly-A/T read (:324-325) leave
+    it as it is.  maxdiff_of(len): bwa_cal_maxdiff for fnr > 0 (never more than thr0)."""
+    cur, out = thr0, []
+    for r in range(first, len(lens)):
+        if n_n[r] > cur:
+            out.append(r)
+        elif not polyat[r]:
+            cur = maxdiff_of(int(lens[r]))
+    return out
+
+
+@functools.lru_cache(maxsize=8)
+def _table(fnr: float):
+    return reads.maxdiff_table(fnr, TABLE_LEN)
+
+
+def _maxdiff_of(opt):
+    if opt["fnr"] > 0:
+        t = _table(opt["fnr"])
+        return lambda l: int(t[l]) if l < len(t) else reads.cal_maxdiff(l, reads.BWA_AVG_ERR, opt["fnr"])
+    return lambda l: opt["max_diff"]
+
+
+# ---------------------------------------------------------------- loading a batch
+def _host_segment(p, thr, md_of, seed_len):
+    """The arrays of a parse_host result as the device loader would leave them."""
+    n = len(p["names"])
+    rec = np.zeros((n, 4), np.uint32)
+    jobs, codes, names, quals, has_q = [], [], [], [], []
+    off = 0
+    for k in range(n):
+        sq = p["seqs"][k]
+        nn = int((sq > 3).sum())
+        poly = len(sq) >= 15 and bool((sq[:15] == 0).all() or (sq[:15] == 3).all())
+        st = HSA_RD_NDROP if nn > thr else HSA_RD_POLYAT if poly else HSA_RD_SEARCHED
+        rec[k] = (st, len(sq), nn, len(jobs) if st == HSA_RD_SEARCHED else 0xFFFFFFFF)
+        if st == HSA_RD_SEARCHED:
+            jobs.append((off, len(sq), md_of(len(sq)), seed_len if seed_len < len(sq) else SEED_NONE, 0))
+            off += len(sq)
+            codes.append(sq)
+            names.append(p["names"][k])
+            quals.append(p["quals"][k] or b"")
+            has_q.append(p["quals"][k] is not None)
+    nb, noff = sam.pack_strings(names)
+    qb, qoff = sam.pack_strings(quals)
+    return dict(rec=rec, jobs=np.array(jobs, JOB_DTYPE) if jobs else np.zeros(0, JOB_DTYPE),
+                codes=np.concatenate(codes) if codes else np.zeros(0, np.uint8), names=nb, name_off=noff, quals=qb,
+                qual_off=qoff, has_qual=np.array(has_q, bool), max_all=max((len(s) for s in p["seqs"]), default=0))
+
+
+def _load_batch(gi, data, pos, opt, d_table, batch_reads, window):
+    """Records of `data` from `pos` on, up to batch_reads: (segments in read order, the
+    offset after them, the window size to go on with).  A device segment is a load_device
+    result, a host segment a parse_host result."""
+    segs, have, host_n = [], 0, 1
+    while have < batch_reads and pos < len(data):
+        w = min(len(data) - pos, window)
+        at_eof = pos + w == len(data)
+        t = reads.load_device(gi, reads.upload(data[pos:pos + w]), w, at_eof, batch_reads - have, opt["max_diff"],
+                              opt["seed_len"], maxdiff=d_table)
+        c, got = t["ctr"], t["n_loaded"]
+        if got:
+            segs.append(dict(kind="dev", t=t, span=(pos, w, at_eof, batch_reads - have)))
+            have += got
+        pos += c["consumed"]
+        if c["bad_record"] != ONES:
+            host_n = 1 if got else min(2 * host_n, 1 << 20)     # (more at a time while the device takes nothing)
+            p = reads.parse_host(data, min(host_n, batch_reads - have), start=pos)
+            if p["names"]:
+                segs.append(dict(kind="host", p=p))
+                have += len(p["names"])
+            pos = p["consumed"]
+            if p["end"] == -2:               # the reference's batch ends at a truncated quality (bwaseqio.c:175)
+                break
+            if p["end"] == -1:
+                pos = len(data)
+        elif got == 0 and c["consumed"] == 0:
+            if at_eof:
+                pos = len(data)
+            else:
+                window *= 2                  # a record longer than the window
+    return segs, pos, window
+
+
+def _merge(gi, data, segs, opt, d_table):
+    """One device batch of the segments: the tensors of load_device's keys, the per-record
+    rows on the host (job indices of the batch), has_qual per job, the batch's threshold."""
+    import torch
+    md_of = _maxdiff_of(opt)
+    max_all = max([s["t"]["ctr"]["max_loaded"] if s["kind"] == "dev" else max(len(x) for x in s["p"]["seqs"]) for s in segs])
+    thr = md_of(max_all)                                   # local_opt.max_diff, bwtaln.c:273-274
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+    parts = []
+    for s in segs:
+        if s["kind"] == "dev":
+            t, n_rec = s["t"], s["t"]["n_loaded"]
+            rec = t["rec"][:4 * n_rec].cpu().numpy().view(np.uint32).reshape(-1, 4).copy()
+            if opt["fnr"] > 0 and t["ctr"]["threshold"] != (thr & ONES) and \
+                    ((rec[:, 0] == HSA_RD_NDROP) & (rec[:, 2].astype(np.int64) <= thr)).any():
+                pos, w, at_eof, room = s["span"]           # the chunk alone set a narrower threshold
+                if max_all < TABLE_LEN:
+                    t = reads.load_device(gi, reads.upload(data[pos:pos + w]), w, at_eof, room, opt["max_diff"], opt["seed_len"],
+                                          maxdiff=d_table, len_floor=max_all)
+                    assert t["n_loaded"] == n_rec and t["ctr"]["threshold"] == (thr & ONES)
+                    rec = t["rec"][:4 * n_rec].cpu().numpy().view(np.uint32).reshape(-1, 4).copy()
+                else:
+                    s = dict(kind="host", p=reads.parse_host(data[pos:pos + t["ctr"]["consumed"]], n_rec))
+        if s["kind"] == "dev":
+            c, n = t["ctr"], t["n_jobs"]
+            parts.append(dict(rec=rec, n=n, jobs=t["jobs"][:n * JOB_DTYPE.itemsize], codes=t["codes"][:c["code_wanted"] - 16],
+                              names=t["names"][:c["name_wanted"]], quals=t["quals"][:c["qual_wanted"]],
+                              name_off=t["name_off"][:n + 1], qual_off=t["qual_off"][:n + 1], has_qual=np.ones(n, bool)))
+        else:
+            h = _host_segment(s["p"], thr, md_of, opt["seed_len"])
+            n = len(h["jobs"])
+            parts.append(dict(rec=h["rec"], n=n, jobs=dev(h["jobs"]), codes=dev(h["codes"]), names=dev(h["names"]),
+                              quals=dev(h["quals"]), name_off=dev(h["name_off"]).view(torch.int64),
+                              qual_off=dev(h["qual_off"]).view(torch.int64), has_qual=h["has_qual"]))
+    jobs, name_off, qual_off, recs = [], [], [], []
+    nj = cb = nb = qb = 0
+    for p in parts:
+        if p["n"]:
+            j = p["jobs"].contiguous().clone().view(torch.int64).view(-1, 3)
+            j[:, 0] += cb                                   # hsa_job_t.off
+            jobs.append(j.view(-1).view(torch.uint8))
+        name_off.append(p["name_off"][:-1] + nb)
+        qual_off.append(p["qual_off"][:-1] + qb)
+        r = p["rec"].copy()
+        r[r[:, 0] == HSA_RD_SEARCHED, 3] += np.uint32(nj)
+        recs.append(r)
+        nj, cb, nb, qb = nj + p["n"], cb + len(p["codes"]), nb + len(p["names"]), qb + len(p["quals"])
+    end = lambda v: torch.tensor([v], dtype=torch.int64, device="cuda")
+    pad = torch.zeros(64, dtype=torch.uint8, device="cuda")
+    rec = np.concatenate(recs)
+    kept = rec[rec[:, 0] == HSA_RD_SEARCHED, 1]
+    return dict(jobs=torch.cat(jobs + [pad[:24]]), codes=torch.cat([p["codes"] for p in parts] + [pad]),
+                names=torch.cat([p["names"] for p in parts] + [pad[:1]]), quals=torch.cat([p["quals"] for p in parts] + [pad[:1]]),
+                name_off=torch.cat(name_off + [end(nb)]), qual_off=torch.cat(qual_off + [end(qb)]), n_jobs=nj, rec=rec,
+                has_qual=np.concatenate([p["has_qual"] for p in parts]), thr=thr, max_all=max_all,
+                max_len=int(kept.max()) if len(kept) else 0)
+
+
+# ---------------------------------------------------------------- search, choose, refine
+def _search(gi, b, first, n, regime, max_seed):
+    """hsa_search_device64 of jobs [first, first + n) of the batch: the device tensors
+    (n_aln, flags, hit_off, hits), run again with more room while reads are left unfinished."""
+    import torch
+    cap = n * 64
+    for _ in range(4):
+        t = dict(n_aln=torch.zeros(n, dtype=torch.int32, device="cuda"), flags=torch.zeros(n, dtype=torch.int32, device="cuda"),
+                 hit_off=torch.zeros(n, dtype=torch.int64, device="cuda"),
+                 hits=torch.zeros(cap * ALN64_WORDS + 2, dtype=torch.int32, device="cuda"),
+                 sc=torch.zeros(16, dtype=torch.int64, device="cuda"))
+        db = DeviceBatch(d_jobs=b["jobs"].data_ptr() + first * JOB_DTYPE.itemsize, n_jobs=n, d_codes=b["codes"].data_ptr(),
+                         d_n_aln=t["n_aln"].data_ptr(), d_flags=t["flags"].data_ptr(), d_hit_off=t["hit_off"].data_ptr(),
+                         d_hits=t["hits"].data_ptr(), hit_cap=cap, d_counters=t["sc"].data_ptr(), max_len=b["max_len"],
+                         max_seed=max_seed)
+        torch.cuda.synchronize()
+        gi.search_device64([regime], db)
+        torch.cuda.synchronize()
+        if int(t["sc"][11]) == 0:
+            t["first"] = first
+            return t
+        cap *= 8
+    raise HsaError("reads left unfinished by the search with 32 768 hit records per read")
+
+
+def _choose(gi, b, t, first, n, state):
+    """hsa_choose_hits_device64 over jobs [first, first + n) of the batch, whose search
+    results are t's (which start at job t["first"]): (outputs, the new state)."""
+    import torch
+    k = first - t["first"]
+    cap = max(n * (N_MULTI + 1), 1)
+    o = dict(sel=torch.zeros(max(n, 1) * 4, dtype=torch.int32, device="cuda"),
+             sel64=torch.zeros(max(n, 1) * 4, dtype=torch.int64, device="cuda"), rng=torch.zeros(1, dtype=torch.int64, device="cuda"),
+             pos_off=torch.zeros(n + 1, dtype=torch.int64, device="cuda"), pos=torch.zeros(cap * 4, dtype=torch.int64, device="cuda"),
+             pos_hit=torch.zeros(cap, dtype=torch.int32, device="cuda"), pos_ctr=torch.zeros(8, dtype=torch.int64, device="cuda"))
+    sub = dict(o, jobs=b["jobs"][first * JOB_DTYPE.itemsize:], codes=b["codes"], n_aln=t["n_aln"][k:], hit_off=t["hit_off"][k:],
+               hits=t["hits"], n_jobs=n, pos_cap=cap, max_len=b["max_len"])
+    cb = ChooseBatch64(d_jobs=sub["jobs"].data_ptr(), n_jobs=n, d_n_aln=sub["n_aln"].data_ptr(), d_hit_off=sub["hit_off"].data_ptr(),
+                       d_hits=sub["hits"].data_ptr(), n_multi=N_MULTI, rng_state=state, d_sel=o["sel"].data_ptr(),
+                       d_sel64=o["sel64"].data_ptr(), d_rng_out=o["rng"].data_ptr(), d_pos_off=o["pos_off"].data_ptr(),
+                       d_pos=o["pos"].data_ptr(), d_pos_hit=o["pos_hit"].data_ptr(), pos_cap=cap, d_counters=o["pos_ctr"].data_ptr())
+    torch.cuda.synchronize()
+    gi.choose_hits64(cb)
+    torch.cuda.synchronize()
+    ctr = o["pos_ctr"].cpu().numpy().view(np.uint64)
+    if int(ctr[6]):
+        raise HsaError(f"read {first + int(ctr[7])} of the batch draws exactly 0.0 (a zero-draw read): not handled")
+    assert int(ctr[0]) == int(ctr[1])
+    return sub, int(o["rng"].cpu().numpy().view(np.uint64)[0])
+
+
+def _refine(gi, sub):
+    """hsa_refine_rows_device64 of the chosen and XA rows; the strides double while a CIGAR or
+    an MD string does not fit."""
+    import torch
+    cs, ms = 16, 128
+    m = sub["pos_cap"]
+    while True:
+        o = dict(rows=torch.zeros(m * RF_ROW_WORDS, dtype=torch.int32, device="cuda"),
+                 rpos=torch.zeros(m * 2, dtype=torch.int64, device="cuda"), cigar=torch.zeros(m * cs, dtype=torch.int32, device="cuda"),
+                 md=torch.zeros(m * ms, dtype=torch.uint8, device="cuda"), ctr=torch.zeros(8, dtype=torch.int64, device="cuda"))
+        rb = RefineBatch64(d_jobs=sub["jobs"].data_ptr(), n_jobs=sub["n_jobs"], d_codes=sub["codes"].data_ptr(),
+                           d_hit_off=sub["hit_off"].data_ptr(), d_hits=sub["hits"].data_ptr(), d_pos_off=sub["pos_off"].data_ptr(),
+                           d_pos=sub["pos"].data_ptr(), d_pos_hit=sub["pos_hit"].data_ptr(), pos_cap=m,
+                           d_pos_counters=sub["pos_ctr"].data_ptr(), max_len=min(max(sub["max_len"], 1), HSA_RF_MAX_LEN),
+                           cigar_stride=cs, md_stride=ms, d_rows=o["rows"].data_ptr(), d_rpos=o["rpos"].data_ptr(),
+                           d_cigar=o["cigar"].data_ptr(), d_md=o["md"].data_ptr(), d_counters=o["ctr"].data_ptr())
+        torch.cuda.synchronize()
+        gi.refine_rows64(rb)
+        torch.cuda.synchronize()
+        if int(o["ctr"][1 + HSA_RF_MD]) == 0 or ms >= 16384:
+            return dict(sub, rows=o["rows"], rpos=o["rpos"], cigar=o["cigar"], md=o["md"], cigar_stride=cs, md_stride=ms)
+        cs, ms = cs * 2, ms * 2
+
+
+def _runs(flags, first, end):
+    """[first, end) cut into runs of equal flags."""
+    out, s = [], first
+    for j in range(first + 1, end + 1):
+        if j == end or flags[j] != flags[s]:
+            out.append((s, j - s))
+            s = j
+    return out if end > first else []
+
+
+def _run_batch(gi, chr_names, b, opt, out, state, stats):
+    """Steps 2 to 5 for a merged batch; returns the generator's state and, per job, whether
+    it got a line."""
+    import torch
+    n = b["n_jobs"]
+    local = dict(opt)                                       # bwtaln.c:254
+    opt["mode"] &= ~MODE_GAPE                               # :261, through aux->opt: it stays
+    local["max_diff"] = b["thr"]                            # :273-274
+    local["max_gapo"] = min(local["max_gapo"], local["max_diff"])       # :275-276
+    n_stacks = (local["max_diff"] + 1) * local["s_mm"] + (local["max_gapo"] + 1) * local["s_gapo"] + \
+        (local["max_gape"] + 1) * local["s_gape"]
+    has_line = np.zeros(n, bool)
+    if n == 0:
+        return state, has_line
+    rg_a, rg_b = regime_of(opt, n_stacks, local["max_diff"]), regime_of(local, n_stacks, local["max_diff"])
+    rec = b["rec"]
+    rec_of_job = np.flatnonzero(rec[:, 0] == HSA_RD_SEARCHED)
+    lens = rec[rec_of_job, 1].astype(np.int64)
+    # bwtaln.c:332 writes through aux->opt: before the switch opt->seed_len itself turns to
+    # "none" at the first searched read that is not longer than it, and stays
+    s0 = opt["seed_len"]
+    plain = np.where(lens > s0, s0, SEED_NONE).astype(np.int32)
+    short = np.flatnonzero(lens <= s0)
+    sticky = plain.copy()
+    if len(short):
+        sticky[short[0]:] = SEED_NONE
+    col = b["jobs"][:n * JOB_DTYPE.itemsize].view(torch.int32).view(-1, 6)[:, 4]
+    set_seeds = lambda a: col.copy_(torch.from_numpy(a).cuda())
+    max_seed = s0 if 0 < s0 < b["max_len"] else 0
+    if not np.array_equal(sticky, plain):
+        set_seeds(sticky)
+    t1 = _search(gi, b, 0, n, rg_a, max_seed)
+    fb = np.flatnonzero(t1["flags"].cpu().numpy() & 1)
+    switch = int(fb[0]) if len(fb) else n                  # the first read without a hit
+    kept_sticky = len(short) and short[0] <= min(switch, n - 1)
+    if kept_sticky:
+        opt["seed_len"] = SEED_NONE
+    parts = _runs(b["has_qual"], 0, min(switch + 1, n))
+    parts = [(t1, f, c) for f, c in parts]
+    stats["searched"] += n
+    if switch < n - 1:
+        first2 = switch + 1
+        seeds2 = sticky if kept_sticky else plain
+        t2 = t1
+        if bytes(rg_a) != bytes(rg_b) or not np.array_equal(seeds2[first2:], sticky[first2:]):
+            if not np.array_equal(seeds2, sticky):
+                set_seeds(seeds2)
+            t2 = _search(gi, b, first2, n - first2, rg_b, max_seed)
+            stats["searched_again"] += n - first2
+        if opt["fnr"] > 0:
+            md_of = _maxdiff_of(opt)
+            r0 = int(rec_of_job[switch]) + 1
+            if (rec[r0:, 2].astype(np.int64) > min(md_of(int(l)) for l in np.unique(rec[r0:, 1]))).any():
+                skip = post_switch_skips(rec[:, 1], rec[:, 2], rec[:, 0] == HSA_RD_POLYAT, r0, md_of, b["thr"])
+                jobs = [int(rec[r, 3]) for r in skip if rec[r, 0] == HSA_RD_SEARCHED]
+                if jobs:                                    # the reference did not search them: no hits
+                    if t2 is t1:
+                        t2 = dict(t1, n_aln=t1["n_aln"].clone())
+                    t2["n_aln"][torch.tensor(jobs, device="cuda") - t2["first"]] = 0
+                    stats["n_drop_after_switch"] += len(jobs)
+        parts += [(t2, f, c) for f, c in _runs(b["has_qual"], first2, n)]
+    for t, first, cnt in parts:
+        sub, state = _choose(gi, b, t, first, cnt, state)
+        m = _refine(gi, sub)
+        q = (b["quals"], b["qual_off"][first:]) if b["has_qual"][first] else None
+        text, _, stat, ctr = sam.device_sam(gi, m, (b["names"], b["name_off"][first:]), q, chr_names, max_top2=opt["max_top2"],
+                                            comp_read=bool(opt["mode"] & MODE_COMPREAD))
+        out.write(text)
+        has_line[first:first + cnt] = stat == 0
+        stats["lines"] += int(ctr[2])
+        stats["refused"] += int(ctr[4]) + int(ctr[5]) + int(ctr[6])
+    return state, has_line
+
+
+def _read_input(data_or_path) -> bytes:
+    if isinstance(data_or_path, (bytes, bytearray, memoryview)):
+        return bytes(data_or_path)
+    with open(data_or_path, "rb") as f:
+        head = f.read(2)
+    op = gzip.open if head == b"\x1f\x8b" else open          # (the reference reads through zlib: either way)
+    with op(data_or_path, "rb") as f:
+        return f.read()
+
+
+def align_fastq(gi, chr_names, data_or_path, opts, out, batch_reads=BATCH_READS, rng_state=HSA_DRAND48_SEED0, unaligned=None):
+    """FASTQ (bytes, or a path; gzip is read through Python's gzip) to SAM text written to
+    `out` (a binary file object), as the module docstring states it.  opts: an option dict
+    (default_opts / parse_options), not modified.  unaligned: a binary file object for the
+    reads without a line.  Returns (the drand48 state after the last read, statistics)."""
+    import collections
+    import torch
+    data = _read_input(data_or_path)
+    opt = dict(opts)
+    if opt.get("trim_qual", 0) != 0 or opt["mode"] & ~(MODE_GAPE | MODE_COMPREAD | MODE_LOGGAP | MODE_NONSTOP):
+        raise ValueError("quality trimming, barcodes, the Casava filter, Illumina-1.3 qualities and BAM input are not built")
+    if not opt["mode"] & MODE_COMPREAD:
+        raise ValueError("colour-space reads (-c) are not built")
+    d_table = torch.from_numpy(_table(opt["fnr"])).cuda() if opt["fnr"] > 0 else None
+    stats = collections.Counter(reads=0, searched=0, searched_again=0, n_drop=0, polyat=0, n_drop_after_switch=0, lines=0,
+                                refused=0, batches=0, device_records=0, host_records=0)
+    pos, state, window = 0, int(rng_state), max(4 << 20, 1024 * int(batch_reads))
+    while pos < len(data):
+        start = pos
+        segs, pos, window = _load_batch(gi, data, pos, opt, d_table, int(batch_reads), window)
+        if not segs:
+            break                                           # bwa_read_seq returned no read: bwtaln.c:477 ends
+        b = _merge(gi, data, segs, opt, d_table)
+        rec = b["rec"]
+        stats["batches"] += 1
+        stats["reads"] += len(rec)
+        stats["n_drop"] += int((rec[:, 0] == HSA_RD_NDROP).sum())
+        stats["polyat"] += int((rec[:, 0] == HSA_RD_POLYAT).sum())
+        stats["device_records"] += sum(s["t"]["n_loaded"] for s in segs if s["kind"] == "dev")
+        stats["host_records"] += sum(len(s["p"]["names"]) for s in segs if s["kind"] == "host")
+        state, has_line = _run_batch(gi, chr_names, b, opt, out, state, stats)
+        if unaligned is not None:
+            p = reads.parse_host(data[start:pos], len(rec))
+            assert len(p["names"]) == len(rec)
+            for r in range(len(rec)):
+                if rec[r, 0] == HSA_RD_SEARCHED and has_line[int(rec[r, 3])]:
+                    continue
+                if p["quals"][r] is None:
+                    unaligned.write(b">" + p["names"][r] + b"\n" + p["raw"][r] + b"\n")
+                else:
+                    unaligned.write(b"@" + p["names"][r] + b"\n" + p["raw"][r] + b"\n+\n" + p["quals"][r] + b"\n")
+    stats["no_line"] = stats["reads"] - stats["lines"]
+    return state, dict(stats)
+
+
+def sam_header(prefix: str) -> bytes:
+    """The @SQ lines of the index, in the reference's format (bwt_print_sam_SQ)."""
+    names, lens = read_chromosomes(prefix)
+    return "".join(f"@SQ\tSN:{n}\tLN:{l}\n" for n, l in zip(names, lens)).encode()
+
+
+def main(argv=None) -> int:
+    argv = sys.argv[1:] if argv is None else argv
+    try:
+        opts, rest, extra = parse_options(argv)
+    except Exception as e:                                  # getopt's and ours
+        print(f"hsa_amd.align: {e}", file=sys.stderr)
+        return 1
+    if len(rest) < 2:
+        print("usage: python -m hsa_amd.align [bwa-aln options] [--header] [--unaligned FILE] [-f OUT] <prefix> <in.fq>",
+              file=sys.stderr)
+        return 1
+    gi, chrs = open_index64(rest[0])
+    out = open(extra["out"], "wb") if extra["out"] else sys.stdout.buffer
+    un = open(extra["unaligned"], "wb") if extra["unaligned"] else None
+    try:
+        if extra["header"]:
+            out.write(sam_header(rest[0]))
+        _, stats = align_fastq(gi, chrs, rest[1], opts, out, unaligned=un)
+        out.flush()
+    finally:
+        if un:
+            un.close()
+        if extra["out"]:
+            out.close()
+        gi.close()
+    print("[hsa_amd.align] " + ", ".join(f"{k} {v}" for k, v in stats.items()), file=sys.stderr)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

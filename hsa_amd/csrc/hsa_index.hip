@@ -122,10 +122,10 @@ extern "C" int hsa_index_release_scratch(hsa_index_t *ix)
     HSA_HIP(hipStreamSynchronize(ix->stream));
     hsa_scratch_free(ix->main); hsa_scratch_free(ix->big); hsa_scratch_free(ix->huge);
     void **bufs[] = {&ix->d_pf, &ix->d_pf2, &ix->d_sp, &ix->d_any, &ix->d_any_aux, &ix->d_help, &ix->d_hp, &ix->d_rf,
-                     &ix->d_ch, &ix->d_sm};
+                     &ix->d_ch, &ix->d_sm, &ix->d_rd};
     size_t *caps[] = {&ix->d_pf_cap, &ix->d_pf2_cap, &ix->d_sp_cap, &ix->d_any_cap, &ix->d_any_aux_cap, &ix->d_help_cap,
-                      &ix->d_hp_cap, &ix->d_rf_cap, &ix->d_ch_cap, &ix->d_sm_cap};
-    for (int i = 0; i < 10; ++i) {
+                      &ix->d_hp_cap, &ix->d_rf_cap, &ix->d_ch_cap, &ix->d_sm_cap, &ix->d_rd_cap};
+    for (int i = 0; i < 11; ++i) {
         if (*bufs[i]) (void)hipFree(*bufs[i]);
         *bufs[i] = nullptr;
         *caps[i] = 0;
@@ -641,6 +641,7 @@ extern "C" void hsa_index_free(hsa_index_t *ix)
     (void)hipFree(ix->d_sa64); (void)hipFree(ix->d_blocks64); (void)hipFree(ix->d_hp);
     (void)hipFree(ix->d_text64); (void)hipFree(ix->d_rf); (void)hipFree(ix->d_ch);
     (void)hipFree(ix->d_sm);
+    (void)hipFree(ix->d_rd);
     if (ix->d_sp) (void)hipFree(ix->d_sp);
     (void)hipFree(ix->d_trie_w);
     (void)hipFree(ix->d_trie_s);
@@ -652,6 +653,8 @@ extern "C" void hsa_index_free(hsa_index_t *ix)
         if (ix->ch_ev[i]) (void)hipEventDestroy(ix->ch_ev[i]);
     for (int i = 0; i <= HSA_SAM_LAUNCHES; ++i)
         if (ix->sm_ev[i]) (void)hipEventDestroy(ix->sm_ev[i]);
+    for (int i = 0; i <= HSA_RD_LAUNCHES; ++i)
+        if (ix->rd_ev[i]) (void)hipEventDestroy(ix->rd_ev[i]);
     for (int i = 0; i < hsa_index::PASS_RING; ++i)
         for (int j = 0; j < 3; ++j)
             if (ix->pev[i][j]) (void)hipEventDestroy(ix->pev[i][j]);

@@ -121,6 +121,10 @@ struct hsa_index {
     void *d_sm = nullptr; size_t d_sm_cap = 0;
     hipEvent_t sm_ev[HSA_SAM_LAUNCHES + 1] = {};   // around its launches (hsa_sam_timing)
     bool sm_timed = false;
+    // hsa_reads_device: newline counts per tile, line starts, per-record fields, the scans
+    void *d_rd = nullptr; size_t d_rd_cap = 0;
+    hipEvent_t rd_ev[HSA_RD_LAUNCHES + 1] = {};    // around its launches (hsa_reads_timing)
+    bool rd_timed = false;
     // the splice path's kernel (hsa_splice.hip): per-lane state, stacks, buffers
     void *d_sp = nullptr; size_t d_sp_cap = 0;
     uint64_t *d_ctr = nullptr;

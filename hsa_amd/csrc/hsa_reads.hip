@@ -1,0 +1,510 @@
+// hsa_reads.hip -- FASTQ bytes to a search batch, on the device.
+//
+// The head of the reference's pipeline: bwa_read_seq (bwaseqio.c:161-231) over kseq_read
+// (kseq.h:155-193), and the read filter and per-read options at the top of
+// bwa_cal_sa_reg_gap (bwtaln.c:313-332).  hsa_reads_device takes the raw bytes of a FASTQ
+// chunk in device memory and leaves d_jobs, d_codes, the names and the qualities in the
+// layouts hsa_search_device64 and hsa_sam_lines_device64 take, and one row per record.
+//
+// The canonical record.  A read is answered exactly or not at all, so only records on which
+// kseq_read provably consumes exactly four lines are parsed here:
+//   line 0  '@', a non-empty name up to the first isspace byte (no NUL in it: the reference
+//           keeps the name with strdup, bwaseqio.c:216), the rest of the line is the comment;
+//   line 1  at least one byte, every byte isgraph and none of '>', '+', '@';
+//   line 2  starts with '+';
+//   line 3  as long as line 1, every byte in 33..127, ended by '\n' or, with at_eof, by the
+//           end of the input.
+// Why kseq_read consumes exactly these lines, given that it starts at the record's '@' with
+// last_char == 0 (true at the start of a file and after every FASTQ record, kseq.h:190):
+//   :161      the skip to the next '>' or '@' stops at once, on the '@';
+//   :166-167  ks_getuntil(0) takes the name up to the first isspace byte; when that byte is
+//             not '\n' the comment runs to the line's '\n' (the line holds no other '\n');
+//   :168-177  the sequence loop stops at '>', '+', '@' or the end; line 1 holds none of them
+//             and only isgraph bytes, so all of line 1 is appended, its '\n' is skipped (not
+//             isgraph) and the loop stops on the '+' that starts line 2;
+//   :185      the rest of the '+' line is skipped through its '\n';
+//   :187-188  the quality loop reads a byte, then tests qual.l < seq.l: every byte of line 3
+//             is in 33..127 and is stored, and with qual.l == seq.l one more byte -- the
+//             '\n' that ends the line, or the end of the input -- is read and dropped;
+//   :190-192  last_char = 0 and the lengths agree: the record is returned, and the next
+//             call starts at the byte after that '\n': the next record's '@'.
+// So in a run of canonical records record k is lines 4k .. 4k + 3, whatever byte a quality
+// line starts with ('@' and '+' included): the record starts are found in parallel by
+// counting newlines, and the question "is this '@' a header or a quality" never arises.
+// Everything else -- a blank line, a sequence over several lines, CRLF ('\r' is not
+// isgraph), FASTA, a quality of another length, an empty name, a read longer than
+// HSA_RD_MAX_LEN or past the max_diff table -- is not canonical.  The first such record stops
+// the load: the records before it are loaded, the counters give its index and byte offset,
+// and the caller hands the bytes from there to a host parser (hsa_amd/reads.py: parse_host).
+//
+// Per canonical record, as the reference:
+//   codes     nst_nt4_table (bwaseqio.c:10-27): ACGT in either case 0..3, '-' 5, others 4.
+//             The table's value is stored; a 5 is not searched differently from a 4 (> 3),
+//             and hsa_sam_lines_device64 refuses a read that holds one (HSA_SAM_INPUT, its
+//             base-code check), as the reference would index "ACGTN"[5];
+//   name      cut at the first isspace byte; a trailing "/1" or "/2" goes when the name is
+//             longer than two bytes (bwaseqio.c:217-220);
+//   quality   as given;
+//   max_diff  opt->max_diff, or with fnr > 0 the entry of the caller's table of
+//             bwa_cal_maxdiff(l) (bwtaln.c:330-331; the table is made on the host: no device
+//             exp enters);
+//   seed_len  opt->seed_len < len ? opt->seed_len : 0x7fffffff (bwtaln.c:332);
+//   filter    more codes > 3 than the batch's threshold: not searched (bwtaln.c:314-317);
+//             first 15 codes all A or all T: not searched (:324-325).  The threshold is
+//             local_opt.max_diff before the option switch (:273-274): the table's entry of
+//             the longest loaded read (or of len_floor, the longest read of the batch's
+//             earlier chunks, when that is longer), or opt->max_diff.  For a read shorter than 15 bases
+//             the reference's memcmp reads past its allocation; such a read is not poly-A/T
+//             here, as the drop-in's host code decides (bwtaln_gpu.c:112, `len >= 15`).
+//
+// Launches, all on one stream, no host round trip, no atomics that place anything:
+//   k_rd_count   one 16-byte load per lane, HSA_RD_TILE bytes per block: newlines per tile;
+//   scan         exclusive, in byte order (rocPRIM): the first line number of every tile;
+//   k_rd_lines   the same loads and a block scan: the start of every line up to 4 M + 1
+//                (M = the most records the call can load);
+//   k_rd_record  one wavefront per 16 consecutive records, lanes along the bytes of a record's
+//                lines: validation, length, N count, poly test, name end, taken from wave-wide
+//                ballots; lane 0 keeps the record's fields; the lowest non-canonical record
+//                by atomicMin (a minimum: order-free);
+//   k_rd_max     the longest loaded read (block maximum, one atomicMax per block);
+//   k_rd_keep    status per record, the three lengths of a kept record for the scan;
+//   scan         exclusive over (jobs, code bytes, name bytes) in record order: a kept
+//                read's job index and offsets, so two runs give equal arrays;
+//   k_rd_rows    one lane per record: its row, its job, its offsets; the counters;
+//   k_rd_bytes   the three byte arrays: one wavefront per 16 consecutive records, lanes along
+//                the bytes of a kept record's name, sequence and quality: a wave's load and
+//                its store each cover 64 contiguous bytes.  No byte at or past a capacity is
+//                touched.
+// The loops of k_rd_record and k_rd_bytes run over a wavefront's records and over 64-byte
+// chunks of one record: their trip counts, their breaks and the branches around the ballots
+// depend on the record alone, which is the same in all 64 lanes, so no lane enters a region
+// alone.  The other kernels' loops hold no barrier and no cross-lane operation.
+//
+// Not built: quality trimming (-q, bwa_trim_read: needs full_len and the XC tag
+// downstream), barcodes (-B), the Casava filter (-Y), Illumina-1.3 qualities (-I), BAM input
+// (-b): non-zero values of those options are HSA_E_ARG.
+#include <cstring>
+#include <hip/hip_runtime.h>
+#include <rocprim/rocprim.hpp>
+#include <string.h>
+
+#include "hsa_internal.h"
+
+#define RD_ONES32 0xFFFFFFFFu
+#define RD_RT 16u                      // records per wavefront of k_rd_record and k_rd_bytes
+#define RD_REFUSED_MODE 0xFF0003E8u   // barcode length, IL13, BAM*, CFY (bwtaln.h:122-131)
+
+struct Rd3 {
+    uint64_t j, c, n;       // jobs, code bytes, name bytes
+};
+struct Rd3Plus {
+    __host__ __device__ Rd3 operator()(const Rd3 &a, const Rd3 &b) const { return Rd3{a.j + b.j, a.c + b.c, a.n + b.n}; }
+};
+
+struct RdArgs {
+    const uint8_t *in;
+    uint32_t n, lead, ntiles, M, ls_last;      // lead: bytes between the aligned base and in
+    int32_t at_eof, max_diff, seed_len, regime;
+    const int32_t *maxdiff;
+    uint32_t n_maxdiff, len_floor;
+    hsa_job_t *jobs; uint64_t job_cap;
+    uint8_t *codes; uint64_t code_cap;
+    uint8_t *names; uint64_t name_cap; uint64_t *name_off;
+    uint8_t *quals; uint64_t qual_cap; uint64_t *qual_off;
+    uint32_t *rec;
+    unsigned long long *ctr;
+    // scratch
+    uint32_t *tile_cnt, *tile_base, *ls, *g;   // g: [0] first non-canonical record, [1] longest loaded, [2] longest kept
+    uint32_t *r_len, *r_nn, *r_fl, *r_name_len;
+    Rd3 *s_in, *s_out;
+};
+
+// The newlines among the 16 bytes at the aligned address of unit u, as a bit mask; bytes
+// outside [0, n) of the input are left out.  b0: the input offset of the unit's byte 0
+__device__ __forceinline__ uint32_t rd_nl_mask(const RdArgs &a, uint64_t u, int64_t &b0)
+{
+    b0 = (int64_t)(16u * u) - (int64_t)a.lead;
+    if (b0 + 16 <= 0 || b0 >= (int64_t)a.n) return 0u;
+    const uint4 w = *reinterpret_cast<const uint4 *>(a.in - a.lead + 16u * u);
+    const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+    uint32_t m = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t x = ws[q] ^ 0x0A0A0A0Au;
+        const uint32_t z = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);    // 0x80 in every zero byte, exact
+        m |= (((z >> 7) & 1u) | ((z >> 14) & 2u) | ((z >> 21) & 4u) | ((z >> 28) & 8u)) << (4 * q);
+    }
+    const uint32_t lo = b0 < 0 ? (uint32_t)(-b0) : 0u;
+    const int64_t left = (int64_t)a.n - b0;
+    const uint32_t hi = left < 16 ? (uint32_t)left : 16u;
+    return m & ((1u << hi) - 1u) & ~((1u << lo) - 1u);
+}
+
+__global__ void __launch_bounds__(256) k_rd_count(RdArgs a)
+{
+    using Reduce = rocprim::block_reduce<uint32_t, 256>;
+    __shared__ typename Reduce::storage_type tmp;
+    int64_t b0;
+    uint32_t c = __popc(rd_nl_mask(a, (uint64_t)blockIdx.x * 256u + threadIdx.x, b0));
+    uint32_t sum = 0;
+    Reduce().reduce(c, sum, tmp);
+    if (threadIdx.x == 0) a.tile_cnt[blockIdx.x] = sum;
+}
+
+// What the newline count says of the input: the records whose four lines are there and
+// ended (cand, at most M), and whether lines of one more record follow them at the end of
+// the input (with at_eof: a non-canonical record cand)
+struct RdShape {
+    uint32_t cand;
+    bool tail_bad;
+};
+__device__ __forceinline__ RdShape rd_shape(const RdArgs &a)
+{
+    const uint32_t nl = a.tile_base[a.ntiles];
+    const bool term = a.n == 0u || a.in[a.n - 1u] == (uint8_t)'\n';
+    const uint64_t lines = (uint64_t)nl + (term ? 0u : 1u);
+    uint64_t full = lines / 4u;
+    const uint32_t rem = (uint32_t)(lines % 4u);
+    if (!term && rem == 0u && !a.at_eof) full -= 1u;       // the last quality line may go on in the next chunk
+    RdShape s;
+    s.tail_bad = a.at_eof && rem != 0u && full < a.M;
+    s.cand = full < a.M ? (uint32_t)full : a.M;
+    return s;
+}
+__device__ __forceinline__ uint32_t rd_loaded(const RdArgs &a, const RdShape &s) { return a.g[0] < s.cand ? a.g[0] : s.cand; }
+
+__global__ void __launch_bounds__(256) k_rd_lines(RdArgs a)
+{
+    using Scan = rocprim::block_scan<uint32_t, 256>;
+    __shared__ typename Scan::storage_type tmp;
+    int64_t b0;
+    const uint32_t m = blockIdx.x < a.ntiles ? rd_nl_mask(a, (uint64_t)blockIdx.x * 256u + threadIdx.x, b0) : 0u;
+    uint32_t before = 0;
+    Scan().exclusive_scan((uint32_t)__popc(m), before, 0u, tmp);
+    uint64_t g = (uint64_t)(blockIdx.x < a.ntiles ? a.tile_base[blockIdx.x] : 0u) + before;     // newlines before this unit
+#pragma unroll
+    for (uint32_t i = 0; i < 16u; ++i)
+        if ((m >> i) & 1u) {
+            ++g;                                            // line g starts after newline g
+            if (g <= a.ls_last) a.ls[g] = (uint32_t)(b0 + i) + 1u;
+        }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        a.ls[0] = 0u;
+        const uint32_t nl = a.tile_base[a.ntiles];
+        // a last line without '\n' ends at n: the start of the line "after" it is n + 1
+        if (a.n && a.in[a.n - 1u] != (uint8_t)'\n' && (uint64_t)nl + 1u <= a.ls_last) a.ls[nl + 1u] = a.n + 1u;
+    }
+}
+
+__device__ __forceinline__ bool rd_space(uint32_t c) { return c == 32u || (c >= 9u && c <= 13u); }
+// nst_nt4_table (bwaseqio.c:10-27)
+__device__ __forceinline__ uint32_t rd_code(uint32_t c)
+{
+    const uint32_t l = c | 0x20u;
+    return l == 'a' ? 0u : l == 'c' ? 1u : l == 'g' ? 2u : l == 't' ? 3u : c == '-' ? 5u : 4u;
+}
+
+// One wavefront per RD_RT consecutive records, the lanes along the bytes of a record's
+// lines: consecutive lanes load consecutive bytes, and what a record's decisions need of
+// them (a byte that is not allowed, the first white space of the header, the codes above 3,
+// the first 15 codes) comes back as wave-wide ballots.  The record, and so every trip
+// count and every branch around a ballot, is the same in all 64 lanes.
+__global__ void __launch_bounds__(64) k_rd_record(RdArgs a)
+{
+    const uint32_t lane = threadIdx.x;
+    const RdShape sh = rd_shape(a);
+    if (blockIdx.x == 0 && lane == 0u && sh.tail_bad) atomicMin(&a.g[0], sh.cand);
+    const uint8_t *in = a.in;
+    for (uint32_t r = 0; r < RD_RT; ++r) {
+        const uint32_t k = blockIdx.x * RD_RT + r;
+        if (k >= sh.cand) break;                            // (the whole wave)
+        const uint32_t s0 = a.ls[4u * k], s1 = a.ls[4u * k + 1u], s2 = a.ls[4u * k + 2u], s3 = a.ls[4u * k + 3u], s4 = a.ls[4u * k + 4u];
+        const uint32_t e0 = s1 - 1u, e1 = s2 - 1u, e2 = s3 - 1u, e3 = s4 - 1u;
+        bool bad = false;
+        uint32_t name_len = 0, len = e1 - s1, nn = 0, poly = 0;
+        // line 0
+        if (e0 - s0 < 2u || in[s0] != (uint8_t)'@') bad = true;
+        else {
+            const uint32_t most = e0 - s0 - 1u > HSA_RD_MAX_LEN ? HSA_RD_MAX_LEN + 1u : e0 - s0 - 1u;
+            name_len = most;
+            for (uint32_t p0 = 0; p0 < most; p0 += 64u) {
+                const uint32_t p = p0 + lane;
+                const uint32_t c = p < most ? in[s0 + 1u + p] : 1u;              // (1: neither white space nor NUL)
+                const unsigned long long sp = __ballot(rd_space(c)), nul = __ballot(c == 0u);
+                if (sp) {
+                    const uint32_t first = (uint32_t)__ffsll((long long)sp) - 1u;
+                    if (nul & ((1ull << first) - 1ull)) bad = true;
+                    name_len = p0 + first;
+                    break;
+                }
+                if (nul) bad = true;
+            }
+            if (name_len == 0u || name_len > HSA_RD_MAX_LEN) bad = true;
+            else if (name_len > 2u && in[s0 + name_len - 1u] == (uint8_t)'/' &&
+                     (in[s0 + name_len] == (uint8_t)'1' || in[s0 + name_len] == (uint8_t)'2'))
+                name_len -= 2u;                             // bwaseqio.c:217-220
+        }
+        // lines 1 and 3
+        if (len < 1u || len > HSA_RD_MAX_LEN || e3 - s3 != len || (a.maxdiff && len >= a.n_maxdiff)) bad = true;
+        else {
+            unsigned long long not_a = 0, not_t = 0;
+            for (uint32_t p0 = 0; p0 < len; p0 += 64u) {
+                const uint32_t p = p0 + lane;
+                const bool on = p < len;
+                const uint32_t c = on ? in[s1 + p] : (uint32_t)'A', q = on ? in[s3 + p] : (uint32_t)'I';
+                const uint32_t code = rd_code(c);
+                if (__ballot(c < 33u || c > 126u || c == '>' || c == '+' || c == '@' || q < 33u || q > 127u)) bad = true;
+                nn += (uint32_t)__popcll(__ballot(on && code > 3u));
+                if (p0 == 0u) {
+                    not_a = __ballot(lane < 15u && (!on || code != 0u));
+                    not_t = __ballot(lane < 15u && (!on || code != 3u));
+                }
+            }
+            poly = len >= 15u && (not_a == 0ull || not_t == 0ull);   // (shorter: bwtaln_gpu.c:112)
+        }
+        // line 2
+        if (e2 - s2 < 1u || in[s2] != (uint8_t)'+') bad = true;
+        if (lane == 0u) {
+            a.r_len[k] = len; a.r_nn[k] = nn; a.r_fl[k] = poly; a.r_name_len[k] = name_len;
+            if (bad) atomicMin(&a.g[0], k);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_rd_max(RdArgs a)
+{
+    __shared__ uint32_t sMax;
+    if (threadIdx.x == 0) sMax = 0u;
+    __syncthreads();
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k < rd_loaded(a, rd_shape(a))) atomicMax(&sMax, a.r_len[k]);
+    __syncthreads();
+    if (threadIdx.x == 0 && sMax) atomicMax(&a.g[1], sMax);
+}
+
+// bwtaln.c:273-274: local_opt.max_diff before the option switch
+__device__ __forceinline__ int32_t rd_threshold(const RdArgs &a)
+{
+    return a.maxdiff ? a.maxdiff[a.g[1] > a.len_floor ? a.g[1] : a.len_floor] : a.max_diff;
+}
+
+__global__ void __launch_bounds__(256) k_rd_keep(RdArgs a)
+{
+    __shared__ uint32_t sMax;
+    if (threadIdx.x == 0) sMax = 0u;
+    __syncthreads();
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k <= a.M) {
+        Rd3 v{0, 0, 0};
+        if (k < rd_loaded(a, rd_shape(a))) {
+            const uint32_t st = (int64_t)a.r_nn[k] > (int64_t)rd_threshold(a) ? HSA_RD_NDROP : a.r_fl[k] ? HSA_RD_POLYAT : HSA_RD_SEARCHED;
+            a.r_fl[k] = st;
+            if (st == HSA_RD_SEARCHED) {
+                v = Rd3{1u, a.r_len[k], a.r_name_len[k]};
+                atomicMax(&sMax, a.r_len[k]);
+            }
+        }
+        a.s_in[k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && sMax) atomicMax(&a.g[2], sMax);
+}
+
+__global__ void __launch_bounds__(256) k_rd_rows(RdArgs a)
+{
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    const RdShape sh = rd_shape(a);
+    const uint32_t loaded = rd_loaded(a, sh);
+    const Rd3 tot = a.s_out[a.M];
+    if (k < loaded) {
+        const uint32_t st = a.r_fl[k], len = a.r_len[k];
+        const Rd3 at = a.s_out[k];
+        const bool kept = st == HSA_RD_SEARCHED;
+        uint32_t *row = a.rec + (size_t)HSA_RD_ROW_WORDS * k;
+        row[0] = st; row[1] = len; row[2] = a.r_nn[k]; row[3] = kept ? (uint32_t)at.j : RD_ONES32;
+        if (kept && at.j <= a.job_cap) {
+            a.name_off[at.j] = at.n;
+            a.qual_off[at.j] = at.c;
+            if (at.j < a.job_cap) {
+                hsa_job_t jb;
+                jb.off = at.c; jb.len = len;
+                jb.max_diff = a.maxdiff ? a.maxdiff[len] : a.max_diff;                    // bwtaln.c:330-331
+                jb.seed_len = a.seed_len < (int32_t)len ? a.seed_len : 0x7fffffff;        // :332
+                jb.regime = a.regime;
+                a.jobs[at.j] = jb;
+            }
+        }
+    }
+    if (k == 0u) {
+        if (tot.j <= a.job_cap) { a.name_off[tot.j] = tot.n; a.qual_off[tot.j] = tot.c; }
+        const uint32_t bad = a.g[0];
+        const bool has_bad = bad <= sh.cand && bad != RD_ONES32;
+        const uint64_t first_left = 4ull * loaded;          // the first line not loaded
+        const uint32_t nl = a.tile_base[a.ntiles];
+        const bool term = a.n == 0u || a.in[a.n - 1u] == (uint8_t)'\n';
+        const uint64_t lines = (uint64_t)nl + (term ? 0u : 1u);
+        unsigned long long *c = a.ctr;
+        c[0] = loaded + (has_bad ? 1u : 0u);
+        c[1] = loaded;
+        c[2] = tot.j; c[3] = tot.j < a.job_cap ? tot.j : a.job_cap;
+        c[4] = tot.c + 16u; c[5] = c[4] < a.code_cap ? c[4] : a.code_cap;
+        c[6] = tot.n; c[7] = tot.n < a.name_cap ? tot.n : a.name_cap;
+        c[8] = tot.c; c[9] = tot.c < a.qual_cap ? tot.c : a.qual_cap;
+        c[10] = first_left < lines ? a.ls[first_left] : a.n;
+        c[11] = has_bad ? bad : ~0ull;
+        c[12] = has_bad ? c[10] : ~0ull;
+        c[13] = a.g[1]; c[14] = a.g[2];
+        c[15] = (unsigned long long)(long long)rd_threshold(a);
+    }
+}
+
+// The three byte arrays: one wavefront per RD_RT consecutive records, the lanes along the
+// bytes of a kept record's name, sequence and quality.  Consecutive lanes load consecutive
+// input bytes and store consecutive output bytes (a wave's store covers 64 contiguous bytes
+// of one array); a byte at or past its array's capacity is not stored.
+__global__ void __launch_bounds__(64) k_rd_bytes(RdArgs a)
+{
+    const uint32_t lane = threadIdx.x;
+    const uint32_t loaded = rd_loaded(a, rd_shape(a));
+    const uint8_t *in = a.in;
+    if (blockIdx.x == 0 && lane < 16u) {                    // the codes' zero padding (hsa_device_batch_t)
+        const uint64_t at = a.s_out[a.M].c + lane;
+        if (at < a.code_cap) a.codes[at] = 0u;
+    }
+    for (uint32_t r = 0; r < RD_RT; ++r) {
+        const uint32_t k = blockIdx.x * RD_RT + r;
+        if (k >= loaded) break;                             // (the whole wave)
+        if (a.r_fl[k] != HSA_RD_SEARCHED) continue;
+        const Rd3 at = a.s_out[k];
+        const uint32_t len = a.r_len[k], nl = a.r_name_len[k];
+        const uint32_t s0 = a.ls[4u * k] + 1u, s1 = a.ls[4u * k + 1u], s3 = a.ls[4u * k + 3u];
+        const uint32_t most = len > nl ? len : nl;
+        for (uint32_t p0 = 0; p0 < most; p0 += 64u) {
+            const uint32_t p = p0 + lane;
+            // (a lane without a byte loads the field's first one, so that no load hides in a branch)
+            const uint32_t c = in[s1 + (p < len ? p : 0u)], q = in[s3 + (p < len ? p : 0u)], m = in[s0 + (p < nl ? p : 0u)];
+            if (p < len) {
+                if (at.c + p < a.code_cap) a.codes[at.c + p] = (uint8_t)rd_code(c);
+                if (at.c + p < a.qual_cap) a.quals[at.c + p] = (uint8_t)q;
+            }
+            if (p < nl && at.n + p < a.name_cap) a.names[at.n + p] = (uint8_t)m;
+        }
+    }
+}
+
+static int g_rd_timing = 0;
+
+extern "C" void hsa_reads_timing(int on) { g_rd_timing = on; }
+
+extern "C" int hsa_reads_launch_times(hsa_index_t *ix, float *ms)
+{
+    if (!ix || !ms) { hsa_set_error("hsa_reads_launch_times: null argument"); return HSA_E_ARG; }
+    if (!ix->rd_timed) { hsa_set_error("hsa_reads_launch_times: the last call was not timed (hsa_reads_timing)"); return HSA_E_ARG; }
+    HSA_HIP(hipSetDevice(ix->device));
+    HSA_HIP(hipEventSynchronize(ix->rd_ev[HSA_RD_LAUNCHES]));
+    for (int i = 0; i < HSA_RD_LAUNCHES; ++i) HSA_HIP(hipEventElapsedTime(&ms[i], ix->rd_ev[i], ix->rd_ev[i + 1]));
+    return 0;
+}
+
+static size_t rd_up(size_t v) { return (v + 255) & ~(size_t)255; }
+
+extern "C" int hsa_reads_device(hsa_index_t *ix, const hsa_reads_batch_t *b, void *stream)
+{
+    const char *what = "hsa_reads_device";
+    if (!ix) {
+        int nd = 0;
+        if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) { hsa_set_error("%s: no HIP device visible", what); return HSA_E_NODEV; }
+        hsa_set_error("%s: null handle", what);
+        return HSA_E_ARG;
+    }
+    if (!b || !b->d_counters || !b->d_rec || !b->d_name_off || !b->d_qual_off || (b->n_in && !b->d_in) ||
+        (b->job_cap && !b->d_jobs) || (b->code_cap && !b->d_codes) || (b->name_cap && !b->d_names) ||
+        (b->qual_cap && !b->d_quals)) {
+        hsa_set_error("%s: null argument", what);
+        return HSA_E_ARG;
+    }
+    if (b->n_in >= 0xFFFFFF00ull || b->max_records < 1u || b->max_records > (1u << 28) || (b->at_eof != 0 && b->at_eof != 1) ||
+        (b->d_maxdiff && b->len_floor >= b->n_maxdiff) || b->job_cap > (1ull << 32)) {
+        hsa_set_error("%s: n_in under 2^32 - 256, max_records in 1..2^28, at_eof 0 or 1, len_floor inside the table", what);
+        return HSA_E_ARG;
+    }
+    if (b->trim_qual != 0 || (b->mode & RD_REFUSED_MODE)) {
+        hsa_set_error("%s: quality trimming, barcodes, the Casava filter, Illumina-1.3 qualities and BAM input are not built", what);
+        return HSA_E_ARG;
+    }
+    HSA_HIP(hipSetDevice(ix->device));
+    hipStream_t st = stream ? (hipStream_t)stream : ix->stream;
+    RdArgs A;
+    A.in = b->d_in; A.n = (uint32_t)b->n_in;
+    A.lead = b->n_in ? (uint32_t)(reinterpret_cast<uintptr_t>(b->d_in) & 15u) : 0u;
+    A.ntiles = (uint32_t)(((uint64_t)A.lead + A.n + HSA_RD_TILE - 1u) / HSA_RD_TILE);
+    const uint64_t most = b->n_in / 8u + 1u;                // (the shortest record has 8 bytes)
+    A.M = (uint32_t)(most < b->max_records ? most : b->max_records);
+    A.ls_last = 4u * A.M + 1u;
+    A.at_eof = b->at_eof; A.max_diff = b->max_diff; A.seed_len = b->seed_len; A.regime = b->regime;
+    A.maxdiff = b->d_maxdiff; A.n_maxdiff = b->n_maxdiff; A.len_floor = b->len_floor;
+    A.jobs = b->d_jobs; A.job_cap = b->job_cap; A.codes = b->d_codes; A.code_cap = b->code_cap;
+    A.names = b->d_names; A.name_cap = b->name_cap; A.name_off = b->d_name_off;
+    A.quals = b->d_quals; A.qual_cap = b->qual_cap; A.qual_off = b->d_qual_off;
+    A.rec = b->d_rec; A.ctr = (unsigned long long *)b->d_counters;
+    size_t tmp1 = 0, tmp2 = 0;
+    HSA_HIP(rocprim::exclusive_scan(nullptr, tmp1, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, (size_t)A.ntiles + 1, rocprim::plus<uint32_t>(), st));
+    HSA_HIP(rocprim::exclusive_scan(nullptr, tmp2, (Rd3 *)nullptr, (Rd3 *)nullptr, Rd3{0, 0, 0}, (size_t)A.M + 1, Rd3Plus(), st));
+    const size_t tile_b = rd_up(((size_t)A.ntiles + 1) * 4), ls_b = rd_up(((size_t)A.ls_last + 1) * 4), rec_b = rd_up((size_t)A.M * 4),
+                 scan_b = rd_up(((size_t)A.M + 1) * sizeof(Rd3)), tmp_b = rd_up(tmp1 > tmp2 ? tmp1 : tmp2);
+    if (int rc = hsa_grow(&ix->d_rd, &ix->d_rd_cap, 2 * tile_b + ls_b + 4 * rec_b + 2 * scan_b + tmp_b + 512)) return rc;
+    char *p = (char *)ix->d_rd;
+    A.g = (uint32_t *)p; p += 256;
+    A.tile_cnt = (uint32_t *)p; p += tile_b;
+    A.tile_base = (uint32_t *)p; p += tile_b;
+    A.ls = (uint32_t *)p; p += ls_b;
+    A.r_len = (uint32_t *)p; p += rec_b;
+    A.r_nn = (uint32_t *)p; p += rec_b;
+    A.r_fl = (uint32_t *)p; p += rec_b;
+    A.r_name_len = (uint32_t *)p; p += rec_b;
+    A.s_in = (Rd3 *)p; p += scan_b;
+    A.s_out = (Rd3 *)p; p += scan_b;
+    void *d_tmp = p;
+    const bool timed = g_rd_timing != 0;
+    if (timed)
+        for (int i = 0; i <= HSA_RD_LAUNCHES; ++i)
+            if (!ix->rd_ev[i]) HSA_HIP(hipEventCreate(&ix->rd_ev[i]));
+    ix->rd_timed = false;
+#define RD_MARK(i) do { if (timed) HSA_HIP(hipEventRecord(ix->rd_ev[i], st)); } while (0)
+    RD_MARK(0);
+    HSA_HIP(hipMemsetAsync(A.g, 0xFF, 4, st));               // no non-canonical record yet
+    HSA_HIP(hipMemsetAsync(A.g + 1, 0, 28, st));
+    HSA_HIP(hipMemsetAsync(A.tile_cnt + A.ntiles, 0, 4, st));
+    // (a line start the input does not reach is never read; zeroed so that no run depends on an earlier one)
+    HSA_HIP(hipMemsetAsync(A.ls, 0, ((size_t)A.ls_last + 1) * 4, st));
+    if (A.ntiles) {
+        hipLaunchKernelGGL(k_rd_count, dim3(A.ntiles), dim3(256), 0, st, A);
+        HSA_HIP(hipGetLastError());
+    }
+    RD_MARK(1);
+    HSA_HIP(rocprim::exclusive_scan(d_tmp, tmp1, A.tile_cnt, A.tile_base, 0u, (size_t)A.ntiles + 1, rocprim::plus<uint32_t>(), st));
+    RD_MARK(2);
+    hipLaunchKernelGGL(k_rd_lines, dim3(A.ntiles ? A.ntiles : 1u), dim3(256), 0, st, A);
+    HSA_HIP(hipGetLastError());
+    RD_MARK(3);
+    const unsigned rb = (A.M + 1u + 255u) / 256u, wb = (A.M + RD_RT - 1u) / RD_RT;
+    hipLaunchKernelGGL(k_rd_record, dim3(wb), dim3(64), 0, st, A);
+    HSA_HIP(hipGetLastError());
+    RD_MARK(4);
+    hipLaunchKernelGGL(k_rd_max, dim3(rb), dim3(256), 0, st, A);
+    HSA_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_rd_keep, dim3(rb), dim3(256), 0, st, A);
+    HSA_HIP(hipGetLastError());
+    RD_MARK(5);
+    HSA_HIP(rocprim::exclusive_scan(d_tmp, tmp2, A.s_in, A.s_out, Rd3{0, 0, 0}, (size_t)A.M + 1, Rd3Plus(), st));
+    RD_MARK(6);
+    hipLaunchKernelGGL(k_rd_rows, dim3(rb), dim3(256), 0, st, A);
+    HSA_HIP(hipGetLastError());
+    RD_MARK(7);
+    hipLaunchKernelGGL(k_rd_bytes, dim3(wb), dim3(64), 0, st, A);
+    HSA_HIP(hipGetLastError());
+    RD_MARK(8);
+#undef RD_MARK
+    ix->rd_timed = timed;
+    return 0;
+}

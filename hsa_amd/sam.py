@@ -113,11 +113,17 @@ def device_sam(gi, dev, names, quals, chr_names, max_top2=30, flag=0, comp_read=
     keys jobs, codes, n_aln, hit_off, hits, n_jobs (the search batch, or a sub-range's offset
     views), sel, sel64, pos_off, pos, pos_hit, pos_cap, pos_ctr (optional: the choice's
     counters), rows, rpos, cigar, md, cigar_stride, md_stride.  names: the reads' names
-    (FASTQ comment cut); quals: their quality strings, or None ("*"); chr_names: by chrID."""
+    (FASTQ comment cut); quals: their quality strings, or None ("*"); chr_names: by chrID.
+    Names and qualities that are on the device already (hsa_amd.reads.load_device) are given
+    as a pair of tensors instead of a list: (the bytes, the n + 1 u64 offsets of these reads; a
+    sub-range's offsets are a view from its first read on)."""
     import torch
     from ._lib import JOB_DTYPE, SamBatch64
     n = int(dev["n_jobs"])
-    if len(names) != n or (quals is not None and len(quals) != n):
+    on_dev = isinstance(names, tuple)
+    if quals is not None and on_dev != isinstance(quals, tuple):
+        raise ValueError("names and qualities come both as lists or both as device tensors")
+    if not on_dev and (len(names) != n or (quals is not None and len(quals) != n)):
         raise ValueError(f"{n} reads, {len(names)} names" + ("" if quals is None else f", {len(quals)} qualities"))
 
     def up(a):
@@ -125,12 +131,19 @@ def device_sam(gi, dev, names, quals, chr_names, max_top2=30, flag=0, comp_read=
         a = a.view(f"i{a.dtype.itemsize}") if a.dtype.kind == "u" and a.dtype.itemsize > 1 else a
         return torch.from_numpy(a if len(a) else np.zeros(1, a.dtype)).cuda()
 
-    nb, noff = pack_strings(names)
     cb, coff = pack_strings(chr_names)
-    t = dict(names=up(nb), name_off=up(noff), chrs=up(cb), chr_off=up(coff))
-    if quals is not None:
-        qb, qoff = pack_strings(quals)
-        t.update(quals=up(qb), qual_off=up(qoff))
+    if on_dev:
+        noff = names[1][:n + 1].cpu().numpy().view(np.uint64)
+        nb = np.zeros(int(noff[-1] - noff[0]) if n else 0, np.uint8)        # (its length sizes the room below)
+        t = dict(names=names[0], name_off=names[1], chrs=up(cb), chr_off=up(coff))
+        if quals is not None:
+            t.update(quals=quals[0], qual_off=quals[1])
+    else:
+        nb, noff = pack_strings(names)
+        t = dict(names=up(nb), name_off=up(noff), chrs=up(cb), chr_off=up(coff))
+        if quals is not None:
+            qb, qoff = pack_strings(quals)
+            t.update(quals=up(qb), qual_off=up(qoff))
     jobs = np.frombuffer(dev["jobs"][:n * JOB_DTYPE.itemsize].cpu().numpy().tobytes(), JOB_DTYPE) if n else np.zeros(0, JOB_DTYPE)
     lens = jobs["len"].astype(np.int64)
     max_xa = int(dev["sel"][:4 * n].view(-1, 4)[:, 3].max().item()) & 0xFFFFFFFF if n else 0

@@ -28,6 +28,9 @@
  *   hsa_refine_rows_device64 -- refine_gapped_core and bwa_cal_md1 (bwtse.c:380-494) with
  *                         aln_global_core (stdaln.c:345-525) for the position rows of a 64-bit
  *                         index: CIGAR, NM and MD.
+ *   hsa_reads_device   -- bwa_read_seq over kseq_read (bwaseqio.c:161-231, kseq.h:155-193) and the
+ *                         read filter of bwa_cal_sa_reg_gap (bwtaln.c:313-332) for FASTQ bytes in
+ *                         device memory.
  *   hsa_extend_batch   -- bwt_extend_backward / bwt_extend_foreward (bwtgap.c:640-663,
  *                         bwt_backtracing_search :346-511): the splice path's seed
  *                         extensions.
@@ -820,6 +823,86 @@ int hsa_sam_lines_device64(hsa_index_t *ix, const hsa_sam_batch64_t *b, void *st
 #define HSA_SAM_LAUNCHES 3
 void hsa_sam_timing(int on);
 int hsa_sam_launch_times(hsa_index_t *ix, float *ms);
+
+/* ---- FASTQ bytes to a search batch ----
+ * bwa_read_seq (bwaseqio.c:161-231) over kseq_read (kseq.h:155-193), and the filter and
+ * per-read options at the top of bwa_cal_sa_reg_gap (bwtaln.c:313-332), for the raw bytes of
+ * a FASTQ chunk that sit in device memory: d_in[0] must be the first byte of a record.  The
+ * call leaves on the device what the later calls take: d_jobs (off, len, max_diff, seed_len,
+ * regime) and d_codes for hsa_search_device64 (zero-padded: 16 zero bytes follow the last
+ * read), d_names / d_name_off and d_quals / d_qual_off for hsa_sam_lines_device64, and one row
+ * per record.  No host round trip; launches on `stream` (NULL = the library's) and does
+ * not synchronise; scratch grows on the handle (hsa_index_release_scratch).  Any index
+ * serves: the handle gives the device, the stream and the scratch.
+ *
+ * Only canonical records are parsed (hsa_amd/csrc/hsa_reads.hip has the argument, with the
+ * kseq.h lines it rests on): '@' and a non-empty name that ends at the first isspace byte
+ * (the comment is dropped); a sequence line of 1..HSA_RD_MAX_LEN bytes, all isgraph and none
+ * of '>', '+', '@'; a line that starts with '+'; a quality line of the sequence's length,
+ * every byte in 33..127, ended by '\n' or, with at_eof, by the end of the input.  The first
+ * record that is not canonical (a blank line, a sequence over several lines, CRLF, FASTA, a
+ * quality of another length, an empty name, a read past HSA_RD_MAX_LEN or, with a table,
+ * of n_maxdiff bases or more) stops the load: the records before it are loaded, [11] and [12]
+ * name it, and the caller parses the bytes from [12] on the host (hsa_amd/reads.py:
+ * parse_host).  With at_eof == 0 an incomplete last record is no error: [10] gives the bytes
+ * consumed and the caller puts the rest in front of its next chunk.  At most max_records
+ * (1..2^28) records are loaded; it sizes the scratch, so state the batch's size.
+ *
+ * Per record: codes through nst_nt4_table (bwaseqio.c:10-27; a '-' is stored as 5, which the
+ * SAM call's base-code check refuses); the name loses a trailing "/1" or "/2" when longer
+ * than two bytes (:217-220); max_diff is `max_diff`, or d_maxdiff[len] when d_maxdiff is
+ * given (fnr > 0: bwa_cal_maxdiff(l) for l < n_maxdiff, computed on the host); seed_len =
+ * seed_len < len ? seed_len : 0x7fffffff (bwtaln.c:332).  A read with more codes above 3 than
+ * the batch's threshold is not searched (:314-317), nor one whose first 15 codes are all A
+ * or all T (:324-325; a read under 15 bases never is, as bwtaln_gpu.c decides).  The threshold is
+ * local_opt.max_diff before the option switch (:273-274): d_maxdiff[longest loaded read], or
+ * max_diff.  A batch that arrives in several chunks states the longest read of its other chunks in
+ * len_floor (under n_maxdiff): the table is then read at the longer of the two.  Kept reads are compacted in record order by a scan: two runs give equal arrays.
+ *
+ * d_rec: HSA_RD_ROW_WORDS u32 per record, max_records rows: status (HSA_RD_*), length, codes
+ * above 3, job index (all-ones: not searched).  Rows of records not loaded are untouched.
+ * d_name_off and d_qual_off hold job_cap + 1 entries.
+ * d_counters (>= 16 u64, written by the call): [0] records seen (the loaded ones and
+ * the one that stopped the load), [1] records loaded, [2] jobs
+ * wanted, [3] written, [4] code bytes wanted (the 16 of padding included), [5] written, [6]
+ * name bytes wanted, [7] written, [8] quality bytes wanted, [9] written, [10] bytes consumed,
+ * [11] the first non-canonical record and [12] its byte offset (all-ones: none), [13] the
+ * longest loaded read, [14] the longest kept read, [15] the threshold (as int64).  wanted >
+ * written: run again with more room; no byte at or past a capacity is touched.
+ *
+ * Not built: quality trimming (-q), barcodes (-B), the Casava filter (-Y), Illumina-1.3
+ * qualities (-I), BAM input (-b): trim_qual != 0 or one of those bits of `mode` (gap_opt_t.mode
+ * as bwa_aln sets it) is HSA_E_ARG, as are null pointers and n_in >= 2^32 - 256. */
+#define HSA_RD_SEARCHED 0u
+#define HSA_RD_NDROP    1u    /* more codes above 3 than the threshold */
+#define HSA_RD_POLYAT   2u    /* the first 15 codes all A or all T */
+#define HSA_RD_ROW_WORDS 4
+#define HSA_RD_MAX_LEN  65535u
+#define HSA_RD_TILE     4096u /* bytes of the input per block of the newline passes */
+typedef struct {
+    const uint8_t *d_in; uint64_t n_in;
+    int32_t at_eof;
+    uint32_t max_records;
+    int32_t max_diff;                /* opt->max_diff (used without a table) */
+    const int32_t *d_maxdiff; uint32_t n_maxdiff;
+    uint32_t len_floor;              /* the longest read of the batch's other chunks, or 0 */
+    int32_t seed_len;                /* opt->seed_len */
+    int32_t regime;                  /* written to every job */
+    int32_t trim_qual; uint32_t mode; /* must select nothing of "Not built" */
+    hsa_job_t *d_jobs; uint64_t job_cap;
+    uint8_t *d_codes; uint64_t code_cap;
+    uint8_t *d_names; uint64_t name_cap; uint64_t *d_name_off;
+    uint8_t *d_quals; uint64_t qual_cap; uint64_t *d_qual_off;
+    uint32_t *d_rec;
+    uint64_t *d_counters;            /* >= 16 u64 */
+} hsa_reads_batch_t;
+int hsa_reads_device(hsa_index_t *ix, const hsa_reads_batch_t *b, void *stream);
+/* Probes, as hsa_sam_timing / hsa_sam_launch_times: the HSA_RD_LAUNCHES times in ms of the
+ * handle's last timed call: k_rd_count (with the memsets), the tile scan, k_rd_lines,
+ * k_rd_record, k_rd_max with k_rd_keep, the record scan, k_rd_rows, k_rd_bytes. */
+#define HSA_RD_LAUNCHES 8
+void hsa_reads_timing(int on);
+int hsa_reads_launch_times(hsa_index_t *ix, float *ms);
 
 #ifdef __cplusplus
 }
