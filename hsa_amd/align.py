@@ -12,7 +12,7 @@ bwa_aln_core does with it (bwtaln.c:452-531):
   3. find the first read without a hit and search the reads after it again with the batch's
      local options (bwtaln.c:363: aux->opt stays &local_opt for the rest of the batch);
   4. choose, refine and write the SAM lines per part, the drand48 state chained through the
-     parts and the batches;
+     parts and the batches (the stage calls of steps 2 to 4: hsa_amd.chain);
   5. append the text to `out`.
 
 What the reference's loop does to its option block is kept over the batches: the GAPE bit
@@ -41,13 +41,12 @@ import sys
 
 import numpy as np
 
-from . import index_io, reads, sam
-from ._lib import (ALN64_WORDS, DRAND48_SEED0, HSA_RD_NDROP, HSA_RD_POLYAT, HSA_RD_SEARCHED, HSA_RF_MAX_LEN, HSA_RF_MD,
-                   JOB_DTYPE, RF_ROW_WORDS, ChooseBatch64, DeviceBatch, GapOpt, GpuIndex, HsaError, RefineBatch64, regime_of)
+from . import chain, index_io, reads, sam
+from ._lib import (DRAND48_SEED0, HSA_RD_NDROP, HSA_RD_POLYAT, HSA_RD_SEARCHED, HSA_RF_MAX_LEN, JOB_DTYPE, GapOpt, GpuIndex,
+                   regime_of)
 
 HSA_DRAND48_SEED0 = DRAND48_SEED0
 BATCH_READS = 0x186A0            # bwtaln.c:477
-N_MULTI = 3                      # bwtaln.c:514
 MODE_GAPE, MODE_COMPREAD, MODE_LOGGAP, MODE_NONSTOP = 0x01, 0x02, 0x04, 0x10
 SEED_NONE = reads.SEED_NONE
 TABLE_LEN = HSA_RF_MAX_LEN + 1   # reads past it go through the host parser (and are not refined)
@@ -270,7 +269,7 @@ def _merge(gi, data, segs, opt, d_table):
     md_of = _maxdiff_of(opt)
     max_all = max([s["t"]["ctr"]["max_loaded"] if s["kind"] == "dev" else max(len(x) for x in s["p"]["seqs"]) for s in segs])
     thr = md_of(max_all)                                   # local_opt.max_diff, bwtaln.c:273-274
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+    dev = chain.to_device
     parts = []
     for s in segs:
         if s["kind"] == "dev":
@@ -295,8 +294,8 @@ def _merge(gi, data, segs, opt, d_table):
             h = _host_segment(s["p"], thr, md_of, opt["seed_len"])
             n = len(h["jobs"])
             parts.append(dict(rec=h["rec"], n=n, jobs=dev(h["jobs"]), codes=dev(h["codes"]), names=dev(h["names"]),
-                              quals=dev(h["quals"]), name_off=dev(h["name_off"]).view(torch.int64),
-                              qual_off=dev(h["qual_off"]).view(torch.int64), has_qual=h["has_qual"]))
+                              quals=dev(h["quals"]), name_off=dev(h["name_off"]), qual_off=dev(h["qual_off"]),
+                              has_qual=h["has_qual"]))
     jobs, name_off, qual_off, recs = [], [], [], []
     nj = cb = nb = qb = 0
     for p in parts:
@@ -321,81 +320,7 @@ def _merge(gi, data, segs, opt, d_table):
                 max_len=int(kept.max()) if len(kept) else 0)
 
 
-# ---------------------------------------------------------------- search, choose, refine
-def _search(gi, b, first, n, regime, max_seed):
-    """hsa_search_device64 of jobs [first, first + n) of the batch: the device tensors
-    (n_aln, flags, hit_off, hits), run again with more room while reads are left unfinished."""
-    import torch
-    cap = n * 64
-    for _ in range(4):
-        t = dict(n_aln=torch.zeros(n, dtype=torch.int32, device="cuda"), flags=torch.zeros(n, dtype=torch.int32, device="cuda"),
-                 hit_off=torch.zeros(n, dtype=torch.int64, device="cuda"),
-                 hits=torch.zeros(cap * ALN64_WORDS + 2, dtype=torch.int32, device="cuda"),
-                 sc=torch.zeros(16, dtype=torch.int64, device="cuda"))
-        db = DeviceBatch(d_jobs=b["jobs"].data_ptr() + first * JOB_DTYPE.itemsize, n_jobs=n, d_codes=b["codes"].data_ptr(),
-                         d_n_aln=t["n_aln"].data_ptr(), d_flags=t["flags"].data_ptr(), d_hit_off=t["hit_off"].data_ptr(),
-                         d_hits=t["hits"].data_ptr(), hit_cap=cap, d_counters=t["sc"].data_ptr(), max_len=b["max_len"],
-                         max_seed=max_seed)
-        torch.cuda.synchronize()
-        gi.search_device64([regime], db)
-        torch.cuda.synchronize()
-        if int(t["sc"][11]) == 0:
-            t["first"] = first
-            return t
-        cap *= 8
-    raise HsaError("reads left unfinished by the search with 32 768 hit records per read")
-
-
-def _choose(gi, b, t, first, n, state):
-    """hsa_choose_hits_device64 over jobs [first, first + n) of the batch, whose search
-    results are t's (which start at job t["first"]): (outputs, the new state)."""
-    import torch
-    k = first - t["first"]
-    cap = max(n * (N_MULTI + 1), 1)
-    o = dict(sel=torch.zeros(max(n, 1) * 4, dtype=torch.int32, device="cuda"),
-             sel64=torch.zeros(max(n, 1) * 4, dtype=torch.int64, device="cuda"), rng=torch.zeros(1, dtype=torch.int64, device="cuda"),
-             pos_off=torch.zeros(n + 1, dtype=torch.int64, device="cuda"), pos=torch.zeros(cap * 4, dtype=torch.int64, device="cuda"),
-             pos_hit=torch.zeros(cap, dtype=torch.int32, device="cuda"), pos_ctr=torch.zeros(8, dtype=torch.int64, device="cuda"))
-    sub = dict(o, jobs=b["jobs"][first * JOB_DTYPE.itemsize:], codes=b["codes"], n_aln=t["n_aln"][k:], hit_off=t["hit_off"][k:],
-               hits=t["hits"], n_jobs=n, pos_cap=cap, max_len=b["max_len"])
-    cb = ChooseBatch64(d_jobs=sub["jobs"].data_ptr(), n_jobs=n, d_n_aln=sub["n_aln"].data_ptr(), d_hit_off=sub["hit_off"].data_ptr(),
-                       d_hits=sub["hits"].data_ptr(), n_multi=N_MULTI, rng_state=state, d_sel=o["sel"].data_ptr(),
-                       d_sel64=o["sel64"].data_ptr(), d_rng_out=o["rng"].data_ptr(), d_pos_off=o["pos_off"].data_ptr(),
-                       d_pos=o["pos"].data_ptr(), d_pos_hit=o["pos_hit"].data_ptr(), pos_cap=cap, d_counters=o["pos_ctr"].data_ptr())
-    torch.cuda.synchronize()
-    gi.choose_hits64(cb)
-    torch.cuda.synchronize()
-    ctr = o["pos_ctr"].cpu().numpy().view(np.uint64)
-    if int(ctr[6]):
-        raise HsaError(f"read {first + int(ctr[7])} of the batch draws exactly 0.0 (a zero-draw read): not handled")
-    assert int(ctr[0]) == int(ctr[1])
-    return sub, int(o["rng"].cpu().numpy().view(np.uint64)[0])
-
-
-def _refine(gi, sub):
-    """hsa_refine_rows_device64 of the chosen and XA rows; the strides double while a CIGAR or
-    an MD string does not fit."""
-    import torch
-    cs, ms = 16, 128
-    m = sub["pos_cap"]
-    while True:
-        o = dict(rows=torch.zeros(m * RF_ROW_WORDS, dtype=torch.int32, device="cuda"),
-                 rpos=torch.zeros(m * 2, dtype=torch.int64, device="cuda"), cigar=torch.zeros(m * cs, dtype=torch.int32, device="cuda"),
-                 md=torch.zeros(m * ms, dtype=torch.uint8, device="cuda"), ctr=torch.zeros(8, dtype=torch.int64, device="cuda"))
-        rb = RefineBatch64(d_jobs=sub["jobs"].data_ptr(), n_jobs=sub["n_jobs"], d_codes=sub["codes"].data_ptr(),
-                           d_hit_off=sub["hit_off"].data_ptr(), d_hits=sub["hits"].data_ptr(), d_pos_off=sub["pos_off"].data_ptr(),
-                           d_pos=sub["pos"].data_ptr(), d_pos_hit=sub["pos_hit"].data_ptr(), pos_cap=m,
-                           d_pos_counters=sub["pos_ctr"].data_ptr(), max_len=min(max(sub["max_len"], 1), HSA_RF_MAX_LEN),
-                           cigar_stride=cs, md_stride=ms, d_rows=o["rows"].data_ptr(), d_rpos=o["rpos"].data_ptr(),
-                           d_cigar=o["cigar"].data_ptr(), d_md=o["md"].data_ptr(), d_counters=o["ctr"].data_ptr())
-        torch.cuda.synchronize()
-        gi.refine_rows64(rb)
-        torch.cuda.synchronize()
-        if int(o["ctr"][1 + HSA_RF_MD]) == 0 or ms >= 16384:
-            return dict(sub, rows=o["rows"], rpos=o["rpos"], cigar=o["cigar"], md=o["md"], cigar_stride=cs, md_stride=ms)
-        cs, ms = cs * 2, ms * 2
-
-
+# ---------------------------------------------------------------- search, choose, refine (hsa_amd.chain)
 def _runs(flags, first, end):
     """[first, end) cut into runs of equal flags."""
     out, s = [], first
@@ -411,16 +336,13 @@ def _run_batch(gi, chr_names, b, opt, out, state, stats):
     it got a line."""
     import torch
     n = b["n_jobs"]
-    local = dict(opt)                                       # bwtaln.c:254
+    local, n_stacks, rg_b = chain.local_regime(opt, b["max_all"])      # bwtaln.c:254, :273-276
+    assert local["max_diff"] == b["thr"]
     opt["mode"] &= ~MODE_GAPE                               # :261, through aux->opt: it stays
-    local["max_diff"] = b["thr"]                            # :273-274
-    local["max_gapo"] = min(local["max_gapo"], local["max_diff"])       # :275-276
-    n_stacks = (local["max_diff"] + 1) * local["s_mm"] + (local["max_gapo"] + 1) * local["s_gapo"] + \
-        (local["max_gape"] + 1) * local["s_gape"]
     has_line = np.zeros(n, bool)
     if n == 0:
         return state, has_line
-    rg_a, rg_b = regime_of(opt, n_stacks, local["max_diff"]), regime_of(local, n_stacks, local["max_diff"])
+    rg_a = regime_of(opt, n_stacks, local["max_diff"])
     rec = b["rec"]
     rec_of_job = np.flatnonzero(rec[:, 0] == HSA_RD_SEARCHED)
     lens = rec[rec_of_job, 1].astype(np.int64)
@@ -437,7 +359,7 @@ def _run_batch(gi, chr_names, b, opt, out, state, stats):
     max_seed = s0 if 0 < s0 < b["max_len"] else 0
     if not np.array_equal(sticky, plain):
         set_seeds(sticky)
-    t1 = _search(gi, b, 0, n, rg_a, max_seed)
+    t1 = chain.search64(gi, b, 0, n, rg_a, max_seed)
     fb = np.flatnonzero(t1["flags"].cpu().numpy() & 1)
     switch = int(fb[0]) if len(fb) else n                  # the first read without a hit
     kept_sticky = len(short) and short[0] <= min(switch, n - 1)
@@ -453,7 +375,7 @@ def _run_batch(gi, chr_names, b, opt, out, state, stats):
         if bytes(rg_a) != bytes(rg_b) or not np.array_equal(seeds2[first2:], sticky[first2:]):
             if not np.array_equal(seeds2, sticky):
                 set_seeds(seeds2)
-            t2 = _search(gi, b, first2, n - first2, rg_b, max_seed)
+            t2 = chain.search64(gi, b, first2, n - first2, rg_b, max_seed)
             stats["searched_again"] += n - first2
         if opt["fnr"] > 0:
             md_of = _maxdiff_of(opt)
@@ -468,8 +390,8 @@ def _run_batch(gi, chr_names, b, opt, out, state, stats):
                     stats["n_drop_after_switch"] += len(jobs)
         parts += [(t2, f, c) for f, c in _runs(b["has_qual"], first2, n)]
     for t, first, cnt in parts:
-        sub, state = _choose(gi, b, t, first, cnt, state)
-        m = _refine(gi, sub)
+        sub, state = chain.choose64(gi, b, t, first, cnt, state)
+        m = chain.refine64(gi, sub)
         q = (b["quals"], b["qual_off"][first:]) if b["has_qual"][first] else None
         text, _, stat, ctr = sam.device_sam(gi, m, (b["names"], b["name_off"][first:]), q, chr_names, max_top2=opt["max_top2"],
                                             comp_read=bool(opt["mode"] & MODE_COMPREAD))

@@ -1,0 +1,223 @@
+"""The device chain of the 64-bit path, stage by stage: search (hsa_search_device64), hit
+positions (hsa_hit_positions_device64), choose (hsa_choose_hits_device64), refine
+(hsa_refine_rows_device64) and the SAM lines (hsa_sam_lines_device64).
+
+The convention.  Everything a stage reads or writes is a device tensor (anything with
+data_ptr()) in one dict, by these keys; a stage returns the dict it was given with its own
+outputs added, so the dict of the last stage holds the whole chain:
+
+  the batch       jobs (hsa_job_t rows as bytes), codes (padded: _lib.pad_codes), n_jobs,
+                  max_len; a sub-range of a batch is the same keys with offset views;
+  search          n_aln, flags, hit_off, hits, sc (the 16 counters), hit_cap, first (the
+                  batch's job the arrays start at);
+  positions       pos_off, pos, pos_hit, pos_ctr (optional for the SAM lines), pos_cap:
+                  written by hit_positions64 or, the chosen and XA rows, by choose64;
+  choose          sel, sel64, rng (the generator's state after the last read);
+  refine          rows, rpos, cigar, md, ctr, cigar_stride, md_stride.
+
+Every stage is a builder and a driver.  The builder (`*_batch`) allocates the outputs and
+returns the filled ctypes struct of _lib with the tensors; a probe builds once and times many
+GpuIndex calls on a stream of its own.  The driver synchronises, calls, synchronises, reads
+the counters and runs the call again with more room where a stage has a retry rule."""
+from __future__ import annotations
+
+import numpy as np
+
+from . import reads
+from ._lib import (ALN64_WORDS, HSA_RF_MAX_LEN, HSA_RF_MD, JOB_DTYPE, RF_ROW_WORDS, ChooseBatch64, DeviceBatch, HitPosBatch64,
+                   HsaError, RefineBatch64, SamBatch64, regime_of)
+
+N_MULTI = 3                      # bwtaln.c:514
+
+
+def to_device(a):
+    """A NumPy array on the device, flat: unsigned types through their signed twins, a
+    structured array (JOB_DTYPE) as its bytes."""
+    import torch
+    a = np.ascontiguousarray(a)
+    if a.dtype.kind == "V":
+        a = a.view(np.uint8)
+    elif a.dtype.kind == "u" and a.dtype.itemsize > 1:
+        a = a.view(f"i{a.dtype.itemsize}")
+    return torch.from_numpy(a.reshape(-1).copy()).cuda()
+
+
+def make_jobs(lens, max_diff, seed_len):
+    """The job rows of reads laid end to end: off the running sum of len, max_diff a value or
+    one per read, seed_len as bwtaln.c:332 sets it (none for a read not longer than it)."""
+    lens = np.asarray(lens, np.uint32)
+    jobs = np.zeros(len(lens), JOB_DTYPE)
+    jobs["off"][1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    jobs["len"] = lens
+    jobs["max_diff"] = max_diff
+    jobs["seed_len"] = np.where(lens > seed_len, seed_len, reads.SEED_NONE)
+    return jobs
+
+
+def local_regime(opt, max_len):
+    """What bwa_cal_sa_reg_gap derives from an option dict for a batch whose longest read has
+    max_len bases (bwtaln.c:254-276): (local_opt, n_stacks, the Regime of local_opt)."""
+    local = dict(opt)
+    if opt["fnr"] > 0:
+        local["max_diff"] = reads.cal_maxdiff(int(max_len), reads.BWA_AVG_ERR, opt["fnr"])
+    local["max_gapo"] = min(local["max_gapo"], local["max_diff"])
+    n_stacks = (local["max_diff"] + 1) * local["s_mm"] + (local["max_gapo"] + 1) * local["s_gapo"] + \
+        (local["max_gape"] + 1) * local["s_gape"]
+    return local, n_stacks, regime_of(local, n_stacks, local["max_diff"])
+
+
+def _new(n, dtype, fill=0):
+    import torch
+    return torch.full((n,), fill, dtype=getattr(torch, dtype), device="cuda")
+
+
+def _ptr(d, k):
+    return d[k].data_ptr() if d.get(k) is not None else None
+
+
+def _call(fn, *args):
+    import torch
+    torch.cuda.synchronize()
+    fn(*args)
+    torch.cuda.synchronize()
+
+
+# ---------------------------------------------------------------- search
+def search64_batch(b, first, n, hit_cap, max_seed):
+    """(DeviceBatch, search tensors) for jobs [first, first + n) of the batch b with room for
+    hit_cap records."""
+    t = dict(n_aln=_new(n, "int32"), flags=_new(n, "int32"), hit_off=_new(n, "int64"),
+             hits=_new(hit_cap * ALN64_WORDS + 2, "int32"), sc=_new(16, "int64"), hit_cap=hit_cap, first=first)
+    db = DeviceBatch(d_jobs=b["jobs"].data_ptr() + first * JOB_DTYPE.itemsize, n_jobs=n, d_codes=b["codes"].data_ptr(),
+                     d_n_aln=t["n_aln"].data_ptr(), d_flags=t["flags"].data_ptr(), d_hit_off=t["hit_off"].data_ptr(),
+                     d_hits=t["hits"].data_ptr(), hit_cap=hit_cap, d_counters=t["sc"].data_ptr(), max_len=b["max_len"],
+                     max_seed=max_seed)
+    return db, t
+
+
+def search64(gi, b, first, n, regime, max_seed, hit_cap=None):
+    """hsa_search_device64 of jobs [first, first + n) of the batch under `regime`: the search
+    tensors.  hit_cap: the records to start with (64 per read); the search runs again with
+    eight times the room while reads are left unfinished, four times in all."""
+    cap = 64 * n if hit_cap is None else hit_cap
+    for _ in range(4):
+        db, t = search64_batch(b, first, n, cap, max_seed)
+        _call(gi.search_device64, [regime], db)
+        if int(t["sc"][11]) == 0:
+            return t
+        cap *= 8
+    raise HsaError("reads left unfinished by the search with 32 768 hit records per read")
+
+
+# ---------------------------------------------------------------- hit positions
+def hit_positions64_batch(t, n, max_occ, fill=0, out=None):
+    """(HitPosBatch64, position tensors) for the hit lists of the search tensors t, up to
+    max_occ rows per read.  fill: what pos and pos_hit hold before the call; out: the
+    position tensors of another builder (of the same pos_cap) to write into instead."""
+    cap = n * max_occ
+    o = out or dict(pos_off=_new(n + 1, "int64"), pos=_new(cap * 4, "int64", fill), pos_hit=_new(cap, "int32", fill),
+                    pos_ctr=_new(8, "int64"))
+    hb = HitPosBatch64(d_n_aln=t["n_aln"].data_ptr(), d_hit_off=t["hit_off"].data_ptr(), d_hits=t["hits"].data_ptr(), n_jobs=n,
+                       max_occ=max_occ, d_pos_off=o["pos_off"].data_ptr(), d_pos=o["pos"].data_ptr(),
+                       d_pos_hit=o["pos_hit"].data_ptr(), pos_cap=cap, d_counters=o["pos_ctr"].data_ptr())
+    return hb, dict(pos_off=o["pos_off"], pos=o["pos"], pos_hit=o["pos_hit"], pos_ctr=o["pos_ctr"], pos_cap=cap)
+
+
+def hit_positions64(gi, t, n, max_occ, fill=0):
+    """hsa_hit_positions_device64 of the search tensors t: t with the position tensors."""
+    hb, o = hit_positions64_batch(t, n, max_occ, fill)
+    _call(gi.hit_positions64, hb)
+    return dict(t, **o)
+
+
+# ---------------------------------------------------------------- choose
+def choose64_batch(b, t, first, n, state, n_multi=N_MULTI):
+    """(ChooseBatch64, the sub-range's dict) for jobs [first, first + n) of the batch b, whose
+    search tensors are t (which start at job t["first"]): offset views of the batch and of
+    the search, the choice's outputs and its rows (pos_cap = n (n_multi + 1))."""
+    k = first - t["first"]
+    cap = max(n * (n_multi + 1), 1)
+    sub = dict(jobs=b["jobs"][first * JOB_DTYPE.itemsize:], codes=b["codes"], n_aln=t["n_aln"][k:], hit_off=t["hit_off"][k:],
+               hits=t["hits"], n_jobs=n, max_len=b["max_len"], sel=_new(max(n, 1) * 4, "int32"),
+               sel64=_new(max(n, 1) * 4, "int64"), rng=_new(1, "int64"), pos_off=_new(n + 1, "int64"),
+               pos=_new(cap * 4, "int64"), pos_hit=_new(cap, "int32"), pos_ctr=_new(8, "int64"), pos_cap=cap)
+    cb = ChooseBatch64(d_jobs=sub["jobs"].data_ptr(), n_jobs=n, d_n_aln=sub["n_aln"].data_ptr(),
+                       d_hit_off=sub["hit_off"].data_ptr(), d_hits=sub["hits"].data_ptr(), n_multi=n_multi, rng_state=state,
+                       d_sel=sub["sel"].data_ptr(), d_sel64=sub["sel64"].data_ptr(), d_rng_out=sub["rng"].data_ptr(),
+                       d_pos_off=sub["pos_off"].data_ptr(), d_pos=sub["pos"].data_ptr(), d_pos_hit=sub["pos_hit"].data_ptr(),
+                       pos_cap=cap, d_counters=sub["pos_ctr"].data_ptr())
+    return cb, sub
+
+
+def choose64(gi, b, t, first, n, state):
+    """hsa_choose_hits_device64 over jobs [first, first + n) of the batch: (the sub-range's
+    dict, the generator's new state).  A zero-draw read is an error."""
+    cb, sub = choose64_batch(b, t, first, n, state)
+    _call(gi.choose_hits64, cb)
+    ctr = sub["pos_ctr"].cpu().numpy().view(np.uint64)
+    if int(ctr[6]):
+        raise HsaError(f"read {first + int(ctr[7])} of the batch draws exactly 0.0 (a zero-draw read): not handled")
+    assert int(ctr[0]) == int(ctr[1])
+    return sub, int(sub["rng"].cpu().numpy().view(np.uint64)[0])
+
+
+# ---------------------------------------------------------------- refine
+def refine64_batch(sub, cigar_stride, md_stride):
+    """(RefineBatch64, sub with the refinement's tensors) for the position rows of sub."""
+    m = sub["pos_cap"]
+    o = dict(sub, rows=_new(m * RF_ROW_WORDS, "int32"), rpos=_new(m * 2, "int64"), cigar=_new(m * cigar_stride, "int32"),
+             md=_new(m * md_stride, "uint8"), ctr=_new(8, "int64"), cigar_stride=cigar_stride, md_stride=md_stride)
+    rb = RefineBatch64(d_jobs=sub["jobs"].data_ptr(), n_jobs=sub["n_jobs"], d_codes=sub["codes"].data_ptr(),
+                       d_hit_off=sub["hit_off"].data_ptr(), d_hits=sub["hits"].data_ptr(), d_pos_off=sub["pos_off"].data_ptr(),
+                       d_pos=sub["pos"].data_ptr(), d_pos_hit=sub["pos_hit"].data_ptr(), pos_cap=m,
+                       d_pos_counters=_ptr(sub, "pos_ctr"), max_len=min(max(sub["max_len"], 1), HSA_RF_MAX_LEN),
+                       cigar_stride=cigar_stride, md_stride=md_stride, d_rows=o["rows"].data_ptr(), d_rpos=o["rpos"].data_ptr(),
+                       d_cigar=o["cigar"].data_ptr(), d_md=o["md"].data_ptr(), d_counters=o["ctr"].data_ptr())
+    return rb, o
+
+
+def refine64(gi, sub, cigar_stride=16, md_stride=128):
+    """hsa_refine_rows_device64 of the rows of sub; both strides double while a CIGAR or an
+    MD string does not fit and md_stride is under 16 384."""
+    while True:
+        rb, o = refine64_batch(sub, cigar_stride, md_stride)
+        _call(gi.refine_rows64, rb)
+        if int(o["ctr"][1 + HSA_RF_MD]) == 0 or md_stride >= 16384:
+            return o
+        cigar_stride, md_stride = cigar_stride * 2, md_stride * 2
+
+
+# ---------------------------------------------------------------- SAM lines
+def sam_lines64_batch(dev, strings, n_chr, max_line, out_cap, flag=0, max_top2=30, comp_read=True):
+    """(SamBatch64, the output tensors line_off, stat, ctr, out) for the chain's dict dev.
+    strings: names, name_off, chrs, chr_off and, unless the lines print "*", quals, qual_off."""
+    import torch
+    n = int(dev["n_jobs"])
+    o = dict(line_off=_new(n + 1, "int64"), stat=_new(max(n, 1), "int32"), ctr=_new(8, "int64"),
+             out=torch.empty(max(out_cap, 1), dtype=torch.uint8, device="cuda"))
+    sb = SamBatch64(d_jobs=_ptr(dev, "jobs"), n_jobs=n, d_codes=_ptr(dev, "codes"), d_n_aln=_ptr(dev, "n_aln"),
+                    d_hit_off=_ptr(dev, "hit_off"), d_hits=_ptr(dev, "hits"), d_sel=_ptr(dev, "sel"), d_sel64=_ptr(dev, "sel64"),
+                    d_pos_off=_ptr(dev, "pos_off"), d_pos=_ptr(dev, "pos"), d_pos_hit=_ptr(dev, "pos_hit"),
+                    pos_cap=int(dev["pos_cap"]), d_pos_counters=_ptr(dev, "pos_ctr"), d_rows=_ptr(dev, "rows"),
+                    d_rpos=_ptr(dev, "rpos"), d_cigar=_ptr(dev, "cigar"), d_md=_ptr(dev, "md"),
+                    cigar_stride=int(dev["cigar_stride"]), md_stride=int(dev["md_stride"]), d_names=strings["names"].data_ptr(),
+                    d_name_off=strings["name_off"].data_ptr(), d_quals=_ptr(strings, "quals"), d_qual_off=_ptr(strings, "qual_off"),
+                    d_chr_names=strings["chrs"].data_ptr(), d_chr_off=strings["chr_off"].data_ptr(), n_chr=n_chr,
+                    flag=int(flag), max_top2=int(max_top2), comp_read=int(bool(comp_read)), max_line=max_line,
+                    d_line_off=o["line_off"].data_ptr(), d_out=o["out"].data_ptr(), out_cap=out_cap,
+                    d_line_stat=o["stat"].data_ptr(), d_counters=o["ctr"].data_ptr())
+    return sb, o
+
+
+def sam_lines64(gi, dev, strings, n_chr, max_line, out_cap, **kw):
+    """hsa_sam_lines_device64 of the chain's dict dev with room for out_cap bytes, run a second
+    time with counters[0] bytes of room when the first reports wanted > written: (the output
+    tensors, the counters as 8 u64 on the host)."""
+    for _ in range(2):
+        sb, o = sam_lines64_batch(dev, strings, n_chr, max_line, out_cap, **kw)
+        _call(gi.sam_lines64, sb)
+        ctr = o["ctr"].cpu().numpy().view(np.uint64)
+        if int(ctr[0]) <= int(ctr[1]):
+            break
+        out_cap = int(ctr[0])
+    return o, ctr

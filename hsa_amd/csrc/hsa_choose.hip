@@ -299,11 +299,7 @@ __global__ void __launch_bounds__(256, 8) k_choose_rows(ChooseArgs a)
     const uint64_t lim = total < a.pos_cap ? total : a.pos_cap;
     if (t == 0) { a.ctr[0] = total; a.ctr[1] = lim; }
     if (t >= lim) return;
-    uint32_t lo = 0, hi = a.n_jobs;            // pos_off[lo] <= t < pos_off[hi]
-    while (hi - lo > 1) {
-        const uint32_t m = lo + ((hi - lo) >> 1);
-        if (a.pos_off[m] <= t) lo = m; else hi = m;
-    }
+    const uint32_t lo = hsa_row_read(a.pos_off, a.n_jobs, t);
     const uint64_t r = t - a.pos_off[lo];
     const uint32_t idx = a.sel[4 * (size_t)lo + 1];
     const uint64_t sa = a.sel64[4 * (size_t)lo];
@@ -340,17 +336,7 @@ static int g_choose_timing = 0;
 
 extern "C" void hsa_choose_timing(int on) { g_choose_timing = on; }
 
-extern "C" int hsa_choose_launch_times(hsa_index_t *ix, float *ms)
-{
-    if (!ix || !ms) { hsa_set_error("hsa_choose_launch_times: null argument"); return HSA_E_ARG; }
-    if (!ix->ch_timed) { hsa_set_error("hsa_choose_launch_times: the last call was not timed (hsa_choose_timing)"); return HSA_E_ARG; }
-    HSA_HIP(hipSetDevice(ix->device));
-    HSA_HIP(hipEventSynchronize(ix->ch_ev[HSA_CH_LAUNCHES]));
-    for (int i = 0; i < HSA_CH_LAUNCHES; ++i) HSA_HIP(hipEventElapsedTime(&ms[i], ix->ch_ev[i], ix->ch_ev[i + 1]));
-    return 0;
-}
-
-static size_t ch_up(size_t v) { return (v + 255) & ~(size_t)255; }
+extern "C" int hsa_choose_launch_times(hsa_index_t *ix, float *ms) { return hsa_stage_times(ix, &hsa_index::ch_t, ms, "hsa_choose"); }
 
 extern "C" int hsa_choose_hits_device64(hsa_index_t *ix, const hsa_choose_batch64_t *b, void *stream)
 {
@@ -367,66 +353,61 @@ extern "C" int hsa_choose_hits_device64(hsa_index_t *ix, const hsa_choose_batch6
     const uint64_t most = n * ((uint64_t)b->n_multi + 1u) < b->pos_cap ? n * ((uint64_t)b->n_multi + 1u) : b->pos_cap;
     if ((most + 255) / 256 > 0x7FFFFFFFull) { hsa_set_error("%s: too many rows", what); return HSA_E_ARG; }
     HSA_HIP(hipSetDevice(ix->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ix->stream;
+    hipStream_t st = hsa_stage_stream(stream, ix->stream);
     size_t tmp_bytes = 0;
-    HSA_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, (ChCls *)nullptr, (ChCls *)nullptr, ChCls{0, 0}, (size_t)(n + 1),
-                                    ChPlus(), st));
-    const size_t cls_b = ch_up((n + 1) * sizeof(ChCls)), u32_b = ch_up((n + 1) * 4), u64_b = ch_up((n + 1) * 8);
-    if (int rc = hsa_grow(&ix->d_ch, &ix->d_ch_cap, 2 * cls_b + 3 * u32_b + 4 * u64_b + ch_up(tmp_bytes) + 256)) return rc;
-    char *p = (char *)ix->d_ch;
+    HSA_TRY(hsa_scan_bytes(tmp_bytes, ChCls{0, 0}, (size_t)(n + 1), ChPlus(), st));
     ChooseArgs A;
+    void *d_tmp = nullptr;
+    auto layout = [&](Carver c) {
+        A.cls = c.take<ChCls>(n + 1);
+        A.scn = c.take<ChCls>(n + 1);
+        A.nbs = c.take<uint32_t>(n + 1);
+        A.var_fix = c.take<uint32_t>(n + 1);
+        A.var_nb = c.take<uint32_t>(n + 1);
+        A.var_hoff = c.take<uint64_t>(n + 1);
+        A.var_A = c.take<uint64_t>(n + 1);
+        A.var_C = c.take<uint64_t>(n + 1);
+        A.var_end = c.take<uint64_t>(n + 1);
+        d_tmp = c.take<char>(tmp_bytes);
+        return c.bytes();
+    };
+    HSA_TRY(hsa_grow(&ix->d_ch, &ix->d_ch_cap, layout(Carver())));
+    layout(Carver(ix->d_ch));
     A.v = hsa_sa_view64(ix, hsa_sa_max_walk());
     A.jobs = b->d_jobs; A.n_aln = b->d_n_aln; A.hit_off = b->d_hit_off; A.hits = b->d_hits; A.log_n = b->d_log_n;
     A.n_jobs = (uint32_t)n; A.n_multi = b->n_multi; A.rng = b->rng_state;
     A.sel = b->d_sel; A.sel64 = b->d_sel64; A.rng_out = b->d_rng_out;
     A.pos_off = b->d_pos_off; A.pos = b->d_pos; A.pos_hit = b->d_pos_hit; A.pos_cap = b->pos_cap;
     A.ctr = (unsigned long long *)b->d_counters;
-    A.cls = (ChCls *)p; p += cls_b;
-    A.scn = (ChCls *)p; p += cls_b;
-    A.nbs = (uint32_t *)p; p += u32_b;
-    A.var_fix = (uint32_t *)p; p += u32_b;
-    A.var_nb = (uint32_t *)p; p += u32_b;
-    A.var_hoff = (uint64_t *)p; p += u64_b;
-    A.var_A = (uint64_t *)p; p += u64_b;
-    A.var_C = (uint64_t *)p; p += u64_b;
-    A.var_end = (uint64_t *)p; p += u64_b;
-    void *d_tmp = p;
     const dim3 per_read((unsigned)((n + 1 + 255) / 256)), blk(256);
-    // HSA_CH_LAUNCHES + 1 events around the launches, only when hsa_choose_timing asked for them
-    const bool timed = g_choose_timing != 0;
-    if (timed)
-        for (int i = 0; i <= HSA_CH_LAUNCHES; ++i)
-            if (!ix->ch_ev[i]) HSA_HIP(hipEventCreate(&ix->ch_ev[i]));
-    ix->ch_timed = false;
-#define CH_MARK(i) do { if (timed) HSA_HIP(hipEventRecord(ix->ch_ev[i], st)); } while (0)
-    CH_MARK(0);
+    StageTimer &tm = ix->ch_t;                 // records only when hsa_choose_timing asked for it
+    HSA_TRY(tm.begin(g_choose_timing != 0));
+    HSA_TRY(tm.mark(0, st));
     HSA_HIP(hipMemsetAsync(b->d_counters, 0, 8 * sizeof(uint64_t), st));
     hipLaunchKernelGGL(k_choose_class, per_read, blk, 0, st, A);
     HSA_HIP(hipGetLastError());
-    CH_MARK(1);
+    HSA_TRY(tm.mark(1, st));
     HSA_HIP(rocprim::exclusive_scan(d_tmp, tmp_bytes, A.cls, A.scn, ChCls{0, 0}, (size_t)(n + 1), ChPlus(), st));
-    CH_MARK(2);
+    HSA_TRY(tm.mark(2, st));
     hipLaunchKernelGGL(k_choose_compact, per_read, blk, 0, st, A);
     HSA_HIP(hipGetLastError());
-    CH_MARK(3);
+    HSA_TRY(tm.mark(3, st));
     if (n) {
         hipLaunchKernelGGL(k_choose_maps, dim3((unsigned)((n + 255) / 256)), blk, 0, st, A);
         HSA_HIP(hipGetLastError());
     }
-    CH_MARK(4);
+    HSA_TRY(tm.mark(4, st));
     if (n) {
         hipLaunchKernelGGL(k_choose_walk, dim3(1), dim3(64), 0, st, A);
         HSA_HIP(hipGetLastError());
     }
-    CH_MARK(5);
+    HSA_TRY(tm.mark(5, st));
     hipLaunchKernelGGL(k_choose_pick, per_read, blk, 0, st, A);
     HSA_HIP(hipGetLastError());
-    CH_MARK(6);
-    const uint64_t blocks = most ? (most + 255) / 256 : 1;     // lane 0 always writes the counters
-    hipLaunchKernelGGL(k_choose_rows, dim3((unsigned)blocks), blk, 0, st, A);
+    HSA_TRY(tm.mark(6, st));
+    hipLaunchKernelGGL(k_choose_rows, dim3(hsa_stage_blocks(most, 256)), blk, 0, st, A);
     HSA_HIP(hipGetLastError());
-    CH_MARK(7);
-#undef CH_MARK
-    ix->ch_timed = timed;
+    HSA_TRY(tm.mark(7, st));
+    tm.end();
     return 0;
 }

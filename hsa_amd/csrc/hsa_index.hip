@@ -109,6 +109,13 @@ int hsa_grow(void **p, size_t *cap, size_t need)
     return 0;
 }
 
+int hsa_stage_times(hsa_index *ix, StageTimer hsa_index::*timer, float *ms, const char *what)
+{
+    if (!ix || !ms) { hsa_set_error("%s_launch_times: null argument", what); return HSA_E_ARG; }
+    HSA_HIP(hipSetDevice(ix->device));
+    return (ix->*timer).times(ms, what);
+}
+
 void hsa_scratch_free(SearchScratch &s)
 {
     (void)hipFree(s.pool); (void)hipFree(s.nxt); (void)hipFree(s.hbuf);
@@ -649,12 +656,7 @@ extern "C" void hsa_index_free(hsa_index_t *ix)
     if (ix->ev1) (void)hipEventDestroy(ix->ev1);
     if (ix->evm) (void)hipEventDestroy(ix->evm);
     if (ix->ev_sp) (void)hipEventDestroy(ix->ev_sp);
-    for (int i = 0; i <= HSA_CH_LAUNCHES; ++i)
-        if (ix->ch_ev[i]) (void)hipEventDestroy(ix->ch_ev[i]);
-    for (int i = 0; i <= HSA_SAM_LAUNCHES; ++i)
-        if (ix->sm_ev[i]) (void)hipEventDestroy(ix->sm_ev[i]);
-    for (int i = 0; i <= HSA_RD_LAUNCHES; ++i)
-        if (ix->rd_ev[i]) (void)hipEventDestroy(ix->rd_ev[i]);
+    for (StageTimer *t : {&ix->ch_t, &ix->sm_t, &ix->rd_t}) t->destroy();
     for (int i = 0; i < hsa_index::PASS_RING; ++i)
         for (int j = 0; j < 3; ++j)
             if (ix->pev[i][j]) (void)hipEventDestroy(ix->pev[i][j]);

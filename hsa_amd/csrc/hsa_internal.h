@@ -19,6 +19,8 @@ void hsa_set_error(const char *fmt, ...);
         }                                                                                   \
     } while (0)
 
+#include "hsa_stage.h"
+
 // The 16 slots of a search's counters (hsa_device_batch_t::d_counters; meanings and
 // values as include/hsa_gpu.h documents them: public ABI).  CTR_Q_*: the queue head a
 // pass takes its jobs from; the forward pass's and the caller-width pass's are internal.
@@ -115,16 +117,13 @@ struct hsa_index {
     void *d_rf = nullptr; size_t d_rf_cap = 0;
     // hsa_choose_hits_device64: per-read classes and their scan, the variable reads' list
     void *d_ch = nullptr; size_t d_ch_cap = 0;
-    hipEvent_t ch_ev[HSA_CH_LAUNCHES + 1] = {};    // around its launches (hsa_choose_timing)
-    bool ch_timed = false;
+    StageTimer ch_t{HSA_CH_LAUNCHES};              // around its launches (hsa_choose_timing)
     // hsa_sam_lines_device64: per-read line lengths and the scan's scratch
     void *d_sm = nullptr; size_t d_sm_cap = 0;
-    hipEvent_t sm_ev[HSA_SAM_LAUNCHES + 1] = {};   // around its launches (hsa_sam_timing)
-    bool sm_timed = false;
+    StageTimer sm_t{HSA_SAM_LAUNCHES};             // around its launches (hsa_sam_timing)
     // hsa_reads_device: newline counts per tile, line starts, per-record fields, the scans
     void *d_rd = nullptr; size_t d_rd_cap = 0;
-    hipEvent_t rd_ev[HSA_RD_LAUNCHES + 1] = {};    // around its launches (hsa_reads_timing)
-    bool rd_timed = false;
+    StageTimer rd_t{HSA_RD_LAUNCHES};              // around its launches (hsa_reads_timing)
     // the splice path's kernel (hsa_splice.hip): per-lane state, stacks, buffers
     void *d_sp = nullptr; size_t d_sp_cap = 0;
     uint64_t *d_ctr = nullptr;
@@ -162,9 +161,13 @@ struct hsa_index {
     int n_clones = 0;                   // live clones of this index
     bool free_pending = false;          // hsa_index_free called while clones were live
 };
+static_assert(HSA_CH_LAUNCHES <= StageTimer::MAX_LAUNCHES && HSA_SAM_LAUNCHES <= StageTimer::MAX_LAUNCHES &&
+              HSA_RD_LAUNCHES <= StageTimer::MAX_LAUNCHES, "a stage with more launches than a StageTimer has events for");
 // HSA_E_ARG when an index's shared arrays may not be replaced (a clone, or an index with
 // live clones)
 int hsa_need_unshared(const hsa_index *ix, const char *what);
+// hsa_<what>_launch_times: the ms per launch of the stage's last timed call; waits for it
+int hsa_stage_times(hsa_index *ix, StageTimer hsa_index::*timer, float *ms, const char *what);
 
 int hsa_grow(void **p, size_t *cap, size_t need);
 int hsa_realloc_device(void **out, void **old, size_t bytes);

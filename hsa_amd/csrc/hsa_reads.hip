@@ -396,17 +396,7 @@ static int g_rd_timing = 0;
 
 extern "C" void hsa_reads_timing(int on) { g_rd_timing = on; }
 
-extern "C" int hsa_reads_launch_times(hsa_index_t *ix, float *ms)
-{
-    if (!ix || !ms) { hsa_set_error("hsa_reads_launch_times: null argument"); return HSA_E_ARG; }
-    if (!ix->rd_timed) { hsa_set_error("hsa_reads_launch_times: the last call was not timed (hsa_reads_timing)"); return HSA_E_ARG; }
-    HSA_HIP(hipSetDevice(ix->device));
-    HSA_HIP(hipEventSynchronize(ix->rd_ev[HSA_RD_LAUNCHES]));
-    for (int i = 0; i < HSA_RD_LAUNCHES; ++i) HSA_HIP(hipEventElapsedTime(&ms[i], ix->rd_ev[i], ix->rd_ev[i + 1]));
-    return 0;
-}
-
-static size_t rd_up(size_t v) { return (v + 255) & ~(size_t)255; }
+extern "C" int hsa_reads_launch_times(hsa_index_t *ix, float *ms) { return hsa_stage_times(ix, &hsa_index::rd_t, ms, "hsa_reads"); }
 
 extern "C" int hsa_reads_device(hsa_index_t *ix, const hsa_reads_batch_t *b, void *stream)
 {
@@ -433,7 +423,7 @@ extern "C" int hsa_reads_device(hsa_index_t *ix, const hsa_reads_batch_t *b, voi
         return HSA_E_ARG;
     }
     HSA_HIP(hipSetDevice(ix->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ix->stream;
+    hipStream_t st = hsa_stage_stream(stream, ix->stream);
     RdArgs A;
     A.in = b->d_in; A.n = (uint32_t)b->n_in;
     A.lead = b->n_in ? (uint32_t)(reinterpret_cast<uintptr_t>(b->d_in) & 15u) : 0u;
@@ -448,30 +438,28 @@ extern "C" int hsa_reads_device(hsa_index_t *ix, const hsa_reads_batch_t *b, voi
     A.quals = b->d_quals; A.qual_cap = b->qual_cap; A.qual_off = b->d_qual_off;
     A.rec = b->d_rec; A.ctr = (unsigned long long *)b->d_counters;
     size_t tmp1 = 0, tmp2 = 0;
-    HSA_HIP(rocprim::exclusive_scan(nullptr, tmp1, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, (size_t)A.ntiles + 1, rocprim::plus<uint32_t>(), st));
-    HSA_HIP(rocprim::exclusive_scan(nullptr, tmp2, (Rd3 *)nullptr, (Rd3 *)nullptr, Rd3{0, 0, 0}, (size_t)A.M + 1, Rd3Plus(), st));
-    const size_t tile_b = rd_up(((size_t)A.ntiles + 1) * 4), ls_b = rd_up(((size_t)A.ls_last + 1) * 4), rec_b = rd_up((size_t)A.M * 4),
-                 scan_b = rd_up(((size_t)A.M + 1) * sizeof(Rd3)), tmp_b = rd_up(tmp1 > tmp2 ? tmp1 : tmp2);
-    if (int rc = hsa_grow(&ix->d_rd, &ix->d_rd_cap, 2 * tile_b + ls_b + 4 * rec_b + 2 * scan_b + tmp_b + 512)) return rc;
-    char *p = (char *)ix->d_rd;
-    A.g = (uint32_t *)p; p += 256;
-    A.tile_cnt = (uint32_t *)p; p += tile_b;
-    A.tile_base = (uint32_t *)p; p += tile_b;
-    A.ls = (uint32_t *)p; p += ls_b;
-    A.r_len = (uint32_t *)p; p += rec_b;
-    A.r_nn = (uint32_t *)p; p += rec_b;
-    A.r_fl = (uint32_t *)p; p += rec_b;
-    A.r_name_len = (uint32_t *)p; p += rec_b;
-    A.s_in = (Rd3 *)p; p += scan_b;
-    A.s_out = (Rd3 *)p; p += scan_b;
-    void *d_tmp = p;
-    const bool timed = g_rd_timing != 0;
-    if (timed)
-        for (int i = 0; i <= HSA_RD_LAUNCHES; ++i)
-            if (!ix->rd_ev[i]) HSA_HIP(hipEventCreate(&ix->rd_ev[i]));
-    ix->rd_timed = false;
-#define RD_MARK(i) do { if (timed) HSA_HIP(hipEventRecord(ix->rd_ev[i], st)); } while (0)
-    RD_MARK(0);
+    HSA_TRY(hsa_scan_bytes(tmp1, 0u, (size_t)A.ntiles + 1, rocprim::plus<uint32_t>(), st));
+    HSA_TRY(hsa_scan_bytes(tmp2, Rd3{0, 0, 0}, (size_t)A.M + 1, Rd3Plus(), st));
+    void *d_tmp = nullptr;
+    auto layout = [&](Carver c) {
+        A.g = c.take<uint32_t>(64);
+        A.tile_cnt = c.take<uint32_t>((size_t)A.ntiles + 1);
+        A.tile_base = c.take<uint32_t>((size_t)A.ntiles + 1);
+        A.ls = c.take<uint32_t>((size_t)A.ls_last + 1);
+        A.r_len = c.take<uint32_t>(A.M);
+        A.r_nn = c.take<uint32_t>(A.M);
+        A.r_fl = c.take<uint32_t>(A.M);
+        A.r_name_len = c.take<uint32_t>(A.M);
+        A.s_in = c.take<Rd3>((size_t)A.M + 1);
+        A.s_out = c.take<Rd3>((size_t)A.M + 1);
+        d_tmp = c.take<char>(tmp1 > tmp2 ? tmp1 : tmp2);
+        return c.bytes();
+    };
+    HSA_TRY(hsa_grow(&ix->d_rd, &ix->d_rd_cap, layout(Carver())));
+    layout(Carver(ix->d_rd));
+    StageTimer &tm = ix->rd_t;                 // records only when hsa_reads_timing asked for it
+    HSA_TRY(tm.begin(g_rd_timing != 0));
+    HSA_TRY(tm.mark(0, st));
     HSA_HIP(hipMemsetAsync(A.g, 0xFF, 4, st));               // no non-canonical record yet
     HSA_HIP(hipMemsetAsync(A.g + 1, 0, 28, st));
     HSA_HIP(hipMemsetAsync(A.tile_cnt + A.ntiles, 0, 4, st));
@@ -481,30 +469,29 @@ extern "C" int hsa_reads_device(hsa_index_t *ix, const hsa_reads_batch_t *b, voi
         hipLaunchKernelGGL(k_rd_count, dim3(A.ntiles), dim3(256), 0, st, A);
         HSA_HIP(hipGetLastError());
     }
-    RD_MARK(1);
+    HSA_TRY(tm.mark(1, st));
     HSA_HIP(rocprim::exclusive_scan(d_tmp, tmp1, A.tile_cnt, A.tile_base, 0u, (size_t)A.ntiles + 1, rocprim::plus<uint32_t>(), st));
-    RD_MARK(2);
+    HSA_TRY(tm.mark(2, st));
     hipLaunchKernelGGL(k_rd_lines, dim3(A.ntiles ? A.ntiles : 1u), dim3(256), 0, st, A);
     HSA_HIP(hipGetLastError());
-    RD_MARK(3);
+    HSA_TRY(tm.mark(3, st));
     const unsigned rb = (A.M + 1u + 255u) / 256u, wb = (A.M + RD_RT - 1u) / RD_RT;
     hipLaunchKernelGGL(k_rd_record, dim3(wb), dim3(64), 0, st, A);
     HSA_HIP(hipGetLastError());
-    RD_MARK(4);
+    HSA_TRY(tm.mark(4, st));
     hipLaunchKernelGGL(k_rd_max, dim3(rb), dim3(256), 0, st, A);
     HSA_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_rd_keep, dim3(rb), dim3(256), 0, st, A);
     HSA_HIP(hipGetLastError());
-    RD_MARK(5);
+    HSA_TRY(tm.mark(5, st));
     HSA_HIP(rocprim::exclusive_scan(d_tmp, tmp2, A.s_in, A.s_out, Rd3{0, 0, 0}, (size_t)A.M + 1, Rd3Plus(), st));
-    RD_MARK(6);
+    HSA_TRY(tm.mark(6, st));
     hipLaunchKernelGGL(k_rd_rows, dim3(rb), dim3(256), 0, st, A);
     HSA_HIP(hipGetLastError());
-    RD_MARK(7);
+    HSA_TRY(tm.mark(7, st));
     hipLaunchKernelGGL(k_rd_bytes, dim3(wb), dim3(64), 0, st, A);
     HSA_HIP(hipGetLastError());
-    RD_MARK(8);
-#undef RD_MARK
-    ix->rd_timed = timed;
+    HSA_TRY(tm.mark(8, st));
+    tm.end();
     return 0;
 }

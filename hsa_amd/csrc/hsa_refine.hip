@@ -102,11 +102,7 @@ __device__ __forceinline__ uint64_t rf_n_rows(const RefineArgs &a)
 // Row t: its read (the last j with pos_off[j] <= t), its record, its position.
 __device__ __forceinline__ void rf_row(const RefineArgs &a, uint64_t t, RfRow &r)
 {
-    uint32_t lo = 0, hi = a.n_jobs;
-    while (hi - lo > 1) {
-        const uint32_t m = lo + ((hi - lo) >> 1);
-        if (a.pos_off[m] <= t) lo = m; else hi = m;
-    }
+    const uint32_t lo = hsa_row_read(a.pos_off, a.n_jobs, t);
     const hsa_job_t jb = a.jobs[lo];
     const uint32_t *rec = a.hits + (a.hit_off[lo] + a.pos_hit[t]) * HSA_ALN64_WORDS;
     const uint32_t w0 = rec[0], w1 = rec[1];
@@ -461,7 +457,7 @@ extern "C" int hsa_refine_rows_device64(hsa_index_t *ix, const hsa_refine_batch6
     if (!ix->wide) { hsa_set_error("%s: not a 64-bit index (hsa_index_create_device64)", what); return HSA_E_ARG; }
     if (!b || b->n_jobs < 0 || !b->d_counters || b->max_len < 0) { hsa_set_error("%s: bad arguments", what); return HSA_E_ARG; }
     HSA_HIP(hipSetDevice(ix->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ix->stream;
+    hipStream_t st = hsa_stage_stream(stream, ix->stream);
     HSA_HIP(hipMemsetAsync(b->d_counters, 0, 8 * sizeof(uint64_t), st));
     if (b->n_jobs == 0 || b->pos_cap == 0) return 0;           // no rows
     if (!b->d_jobs || !b->d_codes || !b->d_hit_off || !b->d_hits || !b->d_pos_off || !b->d_pos || !b->d_pos_hit ||
@@ -496,9 +492,14 @@ extern "C" int hsa_refine_rows_device64(hsa_index_t *ix, const hsa_refine_batch6
     if (waves * wave_bytes > RF_SCRATCH_BUDGET) waves = RF_SCRATCH_BUDGET / wave_bytes;
     if (waves > b->pos_cap) waves = (size_t)b->pos_cap;
     if (waves < 1) waves = 1;
-    const size_t list_bytes = ((size_t)b->pos_cap * 4u + 255u) & ~(size_t)255;
-    if (int rc = hsa_grow(&ix->d_rf, &ix->d_rf_cap, list_bytes + waves * wave_bytes)) return rc;
     RefineArgs A;
+    auto layout = [&](Carver c) {
+        A.list = c.take<uint32_t>((size_t)b->pos_cap);
+        A.wave = c.take<uint8_t>(waves * wave_bytes);
+        return c.bytes();
+    };
+    HSA_TRY(hsa_grow(&ix->d_rf, &ix->d_rf_cap, layout(Carver())));
+    layout(Carver(ix->d_rf));
     A.text = tv;
     A.jobs = b->d_jobs; A.n_jobs = (uint32_t)b->n_jobs; A.codes = b->d_codes;
     A.hit_off = b->d_hit_off; A.hits = b->d_hits;
@@ -507,8 +508,6 @@ extern "C" int hsa_refine_rows_device64(hsa_index_t *ix, const hsa_refine_batch6
     A.max_len = max_len; A.cigar_stride = b->cigar_stride; A.md_stride = b->md_stride;
     A.rows = b->d_rows; A.rpos = b->d_rpos; A.cigar = b->d_cigar; A.md = b->d_md;
     A.ctr = (unsigned long long *)b->d_counters;
-    A.list = (uint32_t *)ix->d_rf;
-    A.wave = (uint8_t *)ix->d_rf + list_bytes;
     A.wave_bytes = wave_bytes; A.tb_bytes = tb_bytes;
     A.tb_stride = tb_stride; A.ring = ring; A.win_cap = win_cap;
     hipLaunchKernelGGL(k_refine_rows, dim3((unsigned)((b->pos_cap + 255u) / 256u)), dim3(256), 0, st, A);

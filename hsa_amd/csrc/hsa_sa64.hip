@@ -147,7 +147,7 @@ extern "C" int hsa_sa_position_device64(hsa_index_t *ix, size_t n, const uint64_
     Sa64Args A;
     A.v = hsa_sa_view64(ix, hsa_sa_max_walk());
     A.idx = d_idx; A.out = d_out4; A.n = n;
-    hipStream_t st = stream ? (hipStream_t)stream : ix->stream;
+    hipStream_t st = hsa_stage_stream(stream, ix->stream);
     if (n) hipLaunchKernelGGL(k_sa_position64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A);
     HSA_HIP(hipGetLastError());
     return 0;
@@ -234,12 +234,7 @@ __global__ void __launch_bounds__(256, 8) k_hitpos_rows(HitPosArgs a)
     const uint64_t lim = total < a.pos_cap ? total : a.pos_cap;
     if (t == 0) { a.ctr[0] = total; a.ctr[1] = lim; }
     if (t >= lim) return;
-    // the read: the last j with pos_off[j] <= t (reads without rows share their successor's offset)
-    uint32_t lo = 0, hi = a.n_jobs;            // pos_off[lo] <= t < pos_off[hi]
-    while (hi - lo > 1) {
-        const uint32_t m = lo + ((hi - lo) >> 1);
-        if (a.pos_off[m] <= t) lo = m; else hi = m;
-    }
+    const uint32_t lo = hsa_row_read(a.pos_off, a.n_jobs, t);
     uint64_t rest = t - a.pos_off[lo];
     // the record and the row within it: rest < the read's rows <= the sum of its records' rows
     const uint32_t *rec = a.hits + a.hit_off[lo] * HSA_ALN64_WORDS;
@@ -268,15 +263,19 @@ extern "C" int hsa_hit_positions_device64(hsa_index_t *ix, const hsa_hitpos_batc
     const uint64_t most = n * b->max_occ < b->pos_cap ? n * b->max_occ : b->pos_cap;   // rows that can be written
     if ((most + 255) / 256 > 0x7FFFFFFFull) { hsa_set_error("hsa_hit_positions_device64: too many rows"); return HSA_E_ARG; }
     HSA_HIP(hipSetDevice(ix->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ix->stream;
-    // scratch: the counts, then the scan's temporary storage
-    const size_t cnt_bytes = ((n + 1) * 8 + 255) & ~(size_t)255;
+    hipStream_t st = hsa_stage_stream(stream, ix->stream);
     size_t tmp_bytes = 0;
-    HSA_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, (uint64_t *)nullptr, b->d_pos_off, (uint64_t)0, (size_t)(n + 1),
-                                    rocprim::plus<uint64_t>(), st));
-    if (int rc = hsa_grow(&ix->d_hp, &ix->d_hp_cap, cnt_bytes + tmp_bytes + 256)) return rc;
-    uint64_t *d_cnt = (uint64_t *)ix->d_hp;
-    void *d_tmp = (char *)ix->d_hp + cnt_bytes;
+    HSA_TRY(hsa_scan_bytes(tmp_bytes, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), st));
+    // scratch: the counts, then the scan's temporary storage
+    uint64_t *d_cnt = nullptr;
+    void *d_tmp = nullptr;
+    auto layout = [&](Carver c) {
+        d_cnt = c.take<uint64_t>(n + 1);
+        d_tmp = c.take<char>(tmp_bytes);
+        return c.bytes();
+    };
+    HSA_TRY(hsa_grow(&ix->d_hp, &ix->d_hp_cap, layout(Carver())));
+    layout(Carver(ix->d_hp));
     HitPosArgs A;
     A.v = hsa_sa_view64(ix, hsa_sa_max_walk());
     A.n_aln = b->d_n_aln; A.hit_off = b->d_hit_off; A.hits = b->d_hits;
@@ -288,8 +287,7 @@ extern "C" int hsa_hit_positions_device64(hsa_index_t *ix, const hsa_hitpos_batc
     HSA_HIP(hipGetLastError());
     HSA_HIP(rocprim::exclusive_scan(d_tmp, tmp_bytes, d_cnt, b->d_pos_off, (uint64_t)0, (size_t)(n + 1),
                                     rocprim::plus<uint64_t>(), st));
-    const uint64_t blocks = most ? (most + 255) / 256 : 1;     // lane 0 always writes the counters
-    hipLaunchKernelGGL(k_hitpos_rows, dim3((unsigned)blocks), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(k_hitpos_rows, dim3(hsa_stage_blocks(most, 256)), dim3(256), 0, st, A);
     HSA_HIP(hipGetLastError());
     return 0;
 }

@@ -440,17 +440,7 @@ static int g_sam_timing = 0;
 
 extern "C" void hsa_sam_timing(int on) { g_sam_timing = on; }
 
-extern "C" int hsa_sam_launch_times(hsa_index_t *ix, float *ms)
-{
-    if (!ix || !ms) { hsa_set_error("hsa_sam_launch_times: null argument"); return HSA_E_ARG; }
-    if (!ix->sm_timed) { hsa_set_error("hsa_sam_launch_times: the last call was not timed (hsa_sam_timing)"); return HSA_E_ARG; }
-    HSA_HIP(hipSetDevice(ix->device));
-    HSA_HIP(hipEventSynchronize(ix->sm_ev[HSA_SAM_LAUNCHES]));
-    for (int i = 0; i < HSA_SAM_LAUNCHES; ++i) HSA_HIP(hipEventElapsedTime(&ms[i], ix->sm_ev[i], ix->sm_ev[i + 1]));
-    return 0;
-}
-
-static size_t sm_up(size_t v) { return (v + 255) & ~(size_t)255; }
+extern "C" int hsa_sam_launch_times(hsa_index_t *ix, float *ms) { return hsa_stage_times(ix, &hsa_index::sm_t, ms, "hsa_sam"); }
 
 extern "C" int hsa_sam_lines_device64(hsa_index_t *ix, const hsa_sam_batch64_t *b, void *stream)
 {
@@ -483,13 +473,18 @@ extern "C" int hsa_sam_lines_device64(hsa_index_t *ix, const hsa_sam_batch64_t *
     }
     const uint64_t n = (uint64_t)b->n_jobs;
     HSA_HIP(hipSetDevice(ix->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ix->stream;
+    hipStream_t st = hsa_stage_stream(stream, ix->stream);
     size_t tmp_bytes = 0;
-    HSA_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0, (size_t)(n + 1),
-                                    rocprim::plus<uint64_t>(), st));
-    const size_t len_b = sm_up((n + 1) * sizeof(uint64_t));
-    if (int rc = hsa_grow(&ix->d_sm, &ix->d_sm_cap, len_b + sm_up(tmp_bytes) + 256)) return rc;
+    HSA_TRY(hsa_scan_bytes(tmp_bytes, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), st));
     SamArgs A;
+    void *d_tmp = nullptr;
+    auto layout = [&](Carver c) {
+        A.lens = c.take<uint64_t>(n + 1);
+        d_tmp = c.take<char>(tmp_bytes);
+        return c.bytes();
+    };
+    HSA_TRY(hsa_grow(&ix->d_sm, &ix->d_sm_cap, layout(Carver())));
+    layout(Carver(ix->d_sm));
     A.jobs = b->d_jobs; A.n_jobs = (uint32_t)n; A.codes = b->d_codes; A.n_aln = b->d_n_aln;
     A.hit_off = b->d_hit_off; A.hits = b->d_hits; A.sel = b->d_sel; A.sel64 = b->d_sel64;
     A.pos_off = b->d_pos_off; A.pos = b->d_pos; A.pos_hit = b->d_pos_hit; A.pos_cap = b->pos_cap;
@@ -505,28 +500,20 @@ extern "C" int hsa_sam_lines_device64(hsa_index_t *ix, const hsa_sam_batch64_t *
     A.lds_text = (A.tile * b->max_line + 16u + 15u) & ~15u;
     A.line_off = b->d_line_off; A.out = b->d_out; A.out_cap = b->out_cap; A.stat = b->d_line_stat;
     A.ctr = (unsigned long long *)b->d_counters;
-    A.lens = (uint64_t *)ix->d_sm;
-    void *d_tmp = (char *)ix->d_sm + len_b;
-    const bool timed = g_sam_timing != 0;
-    if (timed)
-        for (int i = 0; i <= HSA_SAM_LAUNCHES; ++i)
-            if (!ix->sm_ev[i]) HSA_HIP(hipEventCreate(&ix->sm_ev[i]));
-    ix->sm_timed = false;
-#define SM_MARK(i) do { if (timed) HSA_HIP(hipEventRecord(ix->sm_ev[i], st)); } while (0)
-    SM_MARK(0);
+    StageTimer &tm = ix->sm_t;                 // records only when hsa_sam_timing asked for it
+    HSA_TRY(tm.begin(g_sam_timing != 0));
+    HSA_TRY(tm.mark(0, st));
     HSA_HIP(hipMemsetAsync(b->d_counters, 0, 7 * sizeof(uint64_t), st));
     HSA_HIP(hipMemsetAsync(b->d_counters + 7, 0xFF, sizeof(uint64_t), st));      // no refused read yet
     hipLaunchKernelGGL(k_sam_len, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st, A);
     HSA_HIP(hipGetLastError());
-    SM_MARK(1);
+    HSA_TRY(tm.mark(1, st));
     HSA_HIP(rocprim::exclusive_scan(d_tmp, tmp_bytes, A.lens, A.line_off, (uint64_t)0, (size_t)(n + 1),
                                     rocprim::plus<uint64_t>(), st));
-    SM_MARK(2);
-    const uint64_t tiles = n ? (n + A.tile - 1u) / A.tile : 1u;        // lane 0 of block 0 always writes the counters
-    hipLaunchKernelGGL(k_sam_write, dim3((unsigned)tiles), dim3(64), A.lds_text, st, A);
+    HSA_TRY(tm.mark(2, st));
+    hipLaunchKernelGGL(k_sam_write, dim3(hsa_stage_blocks(n, A.tile)), dim3(64), A.lds_text, st, A);
     HSA_HIP(hipGetLastError());
-    SM_MARK(3);
-#undef SM_MARK
-    ix->sm_timed = timed;
+    HSA_TRY(tm.mark(3, st));
+    tm.end();
     return 0;
 }

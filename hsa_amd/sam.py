@@ -109,16 +109,15 @@ def device_sam(gi, dev, names, quals, chr_names, max_top2=30, flag=0, comp_read=
     counters (8 u64)) of one hsa_sam_lines_device64 call, run a second time with
     counters[0] bytes of room when the first reports wanted > written.
 
-    dev: the device tensors of search, choose and refine (anything with data_ptr()) by the
-    keys jobs, codes, n_aln, hit_off, hits, n_jobs (the search batch, or a sub-range's offset
-    views), sel, sel64, pos_off, pos, pos_hit, pos_cap, pos_ctr (optional: the choice's
-    counters), rows, rpos, cigar, md, cigar_stride, md_stride.  names: the reads' names
+    dev: the device tensors of search, choose and refine by the keys of hsa_amd.chain (the
+    dict chain.refine64 returns, or any dict with those keys).  names: the reads' names
     (FASTQ comment cut); quals: their quality strings, or None ("*"); chr_names: by chrID.
     Names and qualities that are on the device already (hsa_amd.reads.load_device) are given
     as a pair of tensors instead of a list: (the bytes, the n + 1 u64 offsets of these reads; a
     sub-range's offsets are a view from its first read on)."""
     import torch
-    from ._lib import JOB_DTYPE, SamBatch64
+    from . import chain
+    from ._lib import JOB_DTYPE
     n = int(dev["n_jobs"])
     on_dev = isinstance(names, tuple)
     if quals is not None and on_dev != isinstance(quals, tuple):
@@ -126,11 +125,7 @@ def device_sam(gi, dev, names, quals, chr_names, max_top2=30, flag=0, comp_read=
     if not on_dev and (len(names) != n or (quals is not None and len(quals) != n)):
         raise ValueError(f"{n} reads, {len(names)} names" + ("" if quals is None else f", {len(quals)} qualities"))
 
-    def up(a):
-        a = np.ascontiguousarray(a)
-        a = a.view(f"i{a.dtype.itemsize}") if a.dtype.kind == "u" and a.dtype.itemsize > 1 else a
-        return torch.from_numpy(a if len(a) else np.zeros(1, a.dtype)).cuda()
-
+    up = lambda a: chain.to_device(a if len(a) else np.zeros(1, a.dtype))       # (no null pointer for an empty array)
     cb, coff = pack_strings(chr_names)
     if on_dev:
         noff = names[1][:n + 1].cpu().numpy().view(np.uint64)
@@ -153,31 +148,8 @@ def device_sam(gi, dev, names, quals, chr_names, max_top2=30, flag=0, comp_read=
     # room: the strings as they are, a typical line's numbers and tags; a batch that needs
     # more says so in counters[0]
     cap = int(len(nb) + (2 if quals is not None else 1) * lens.sum() + n * (160 + max_chr) + 64)
-    o = dict(line_off=torch.zeros(n + 1, dtype=torch.int64, device="cuda"),
-             stat=torch.zeros(max(n, 1), dtype=torch.int32, device="cuda"),
-             ctr=torch.zeros(8, dtype=torch.int64, device="cuda"))
-    ptr = lambda k: dev[k].data_ptr() if dev.get(k) is not None else None
-    for _ in range(2):
-        out = torch.empty(max(cap, 1), dtype=torch.uint8, device="cuda")
-        b = SamBatch64(d_jobs=ptr("jobs"), n_jobs=n, d_codes=ptr("codes"), d_n_aln=ptr("n_aln"), d_hit_off=ptr("hit_off"),
-                       d_hits=ptr("hits"), d_sel=ptr("sel"), d_sel64=ptr("sel64"), d_pos_off=ptr("pos_off"),
-                       d_pos=ptr("pos"), d_pos_hit=ptr("pos_hit"), pos_cap=int(dev["pos_cap"]), d_pos_counters=ptr("pos_ctr"),
-                       d_rows=ptr("rows"), d_rpos=ptr("rpos"), d_cigar=ptr("cigar"), d_md=ptr("md"),
-                       cigar_stride=int(dev["cigar_stride"]), md_stride=int(dev["md_stride"]),
-                       d_names=t["names"].data_ptr(), d_name_off=t["name_off"].data_ptr(),
-                       d_quals=t["quals"].data_ptr() if quals is not None else None,
-                       d_qual_off=t["qual_off"].data_ptr() if quals is not None else None,
-                       d_chr_names=t["chrs"].data_ptr(), d_chr_off=t["chr_off"].data_ptr(), n_chr=len(chr_names),
-                       flag=int(flag), max_top2=int(max_top2), comp_read=int(bool(comp_read)), max_line=max_line,
-                       d_line_off=o["line_off"].data_ptr(), d_out=out.data_ptr(), out_cap=cap,
-                       d_line_stat=o["stat"].data_ptr(), d_counters=o["ctr"].data_ptr())
-        torch.cuda.synchronize()
-        gi.sam_lines64(b)
-        torch.cuda.synchronize()
-        ctr = o["ctr"].cpu().numpy().view(np.uint64)
-        if int(ctr[0]) <= int(ctr[1]):
-            break
-        cap = int(ctr[0])
+    o, ctr = chain.sam_lines64(gi, dev, t, len(chr_names), max_line, cap, flag=flag, max_top2=max_top2, comp_read=comp_read)
+    out = o["out"]
     written = int(ctr[1])
     host = torch.empty(max(written, 1), dtype=torch.uint8).pin_memory()
     host[:written].copy_(out[:written])

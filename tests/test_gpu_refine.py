@@ -11,7 +11,6 @@
 import ctypes as C
 import gzip
 import json
-import math
 import os
 import re
 import subprocess
@@ -21,6 +20,8 @@ import pytest
 
 from golden_io import GOLD, INDEX, parse_opts
 from hsa_amd import index_io
+from hsa_amd.chain import to_device as dev
+from hsa_amd.reads import cal_maxdiff
 
 pytestmark = pytest.mark.gpu
 
@@ -32,15 +33,6 @@ ONES = U64(0xFFFFFFFFFFFFFFFF)
 BIG_T = (1 << 32) + (1 << 22) + 7
 SEED_NONE = 0x7FFFFFFF
 _IX = {}
-
-
-def dev(a):
-    """A NumPy array on the device (unsigned types through their signed twins)."""
-    import torch
-    a = np.ascontiguousarray(a)
-    if a.dtype.kind == "u" and a.dtype.itemsize > 1:
-        a = a.view(f"i{a.dtype.itemsize}")
-    return torch.from_numpy(a.reshape(-1).copy()).cuda()
 
 
 def tiny_like(name, text=True):
@@ -67,59 +59,21 @@ def index_text(name):
     return _IX[name]
 
 
-def cal_maxdiff(l, err=0.02, thres=0.04):
-    """bwa_cal_maxdiff (bwtaln.c:46-58)."""
-    el = math.exp(-l * err)
-    y, x, s = 1.0, 1, el
-    for k in range(1, 1000):
-        y *= l * err
-        x *= k
-        s += el * y / x
-        if 1.0 - s < thres:
-            return k
-    return 2
-
-
 def search_rows(gi, lens, codes, od, max_occ, cap_per_read=64):
     """hsa_search_device64 then hsa_hit_positions_device64 of one batch, everything left
     on the device: (device tensors for the refinement, host copies)."""
-    import torch
-    from hsa_amd._lib import ALN64_WORDS, JOB_DTYPE, DeviceBatch, GapOpt, HitPosBatch64, pad_codes, regime_of
+    from hsa_amd import chain
+    from hsa_amd._lib import ALN64_WORDS, pad_codes, regime_of
     lens = np.asarray(lens, np.uint32)
     n = len(lens)
-    md = np.array([cal_maxdiff(int(l), thres=od["fnr"]) for l in lens], np.int32) if od["fnr"] > 0 else \
-        np.full(n, od["max_diff"], np.int32)
-    loc = dict(od, max_diff=int(cal_maxdiff(int(lens.max()), thres=od["fnr"])) if od["fnr"] > 0 else od["max_diff"])
-    loc["max_gapo"] = min(loc["max_gapo"], loc["max_diff"])
-    n_stacks = (loc["max_diff"] + 1) * od["s_mm"] + (loc["max_gapo"] + 1) * od["s_gapo"] + (od["max_gape"] + 1) * od["s_gape"]
-    rg = regime_of(od, n_stacks, loc["max_diff"])
-    jobs = np.zeros(n, JOB_DTYPE)
-    jobs["off"] = np.concatenate([[0], np.cumsum(lens.astype(np.uint64))[:-1]])
-    jobs["len"] = lens
-    jobs["max_diff"] = md
-    jobs["seed_len"] = np.where(lens > od["seed_len"], od["seed_len"], SEED_NONE)
+    md = np.array([cal_maxdiff(int(l), thres=od["fnr"]) for l in lens], np.int32) if od["fnr"] > 0 else od["max_diff"]
+    loc, n_stacks, _ = chain.local_regime(od, int(lens.max()))
+    jobs = chain.make_jobs(lens, md, od["seed_len"])
+    b = dict(jobs=dev(jobs), codes=dev(pad_codes(codes)), n_jobs=n, max_len=int(lens.max()))
     cap = n * cap_per_read
-    t = dict(jobs=dev(jobs.view(np.uint8)), codes=dev(pad_codes(codes)),
-             n_aln=torch.zeros(n, dtype=torch.int32, device="cuda"), flags=torch.zeros(n, dtype=torch.int32, device="cuda"),
-             hit_off=torch.zeros(n, dtype=torch.int64, device="cuda"),
-             hits=torch.zeros(cap * ALN64_WORDS + 2, dtype=torch.int32, device="cuda"),
-             sc=torch.zeros(16, dtype=torch.int64, device="cuda"),
-             pos_off=torch.zeros(n + 1, dtype=torch.int64, device="cuda"),
-             pos=torch.full((n * max_occ * 4,), 0x77, dtype=torch.int64, device="cuda"),
-             pos_hit=torch.full((n * max_occ,), 0x77, dtype=torch.int32, device="cuda"),
-             pos_ctr=torch.zeros(4, dtype=torch.int64, device="cuda"))
-    b = DeviceBatch(d_jobs=t["jobs"].data_ptr(), n_jobs=n, d_codes=t["codes"].data_ptr(), d_n_aln=t["n_aln"].data_ptr(),
-                    d_flags=t["flags"].data_ptr(), d_hit_off=t["hit_off"].data_ptr(), d_hits=t["hits"].data_ptr(),
-                    hit_cap=cap, d_counters=t["sc"].data_ptr(), max_len=int(lens.max()), max_seed=od["seed_len"])
-    torch.cuda.synchronize()
-    gi.search_device64([rg], b)
-    hp = HitPosBatch64(d_n_aln=t["n_aln"].data_ptr(), d_hit_off=t["hit_off"].data_ptr(), d_hits=t["hits"].data_ptr(),
-                       n_jobs=n, max_occ=max_occ, d_pos_off=t["pos_off"].data_ptr(), d_pos=t["pos"].data_ptr(),
-                       d_pos_hit=t["pos_hit"].data_ptr(), pos_cap=n * max_occ, d_counters=t["pos_ctr"].data_ptr())
-    gi.hit_positions64(hp)
-    torch.cuda.synchronize()
-    assert int(t["sc"][11]) == 0, "reads left unfinished"
-    t.update(n_jobs=n, max_len=int(lens.max()), pos_cap=n * max_occ)
+    t = chain.search64(gi, b, 0, n, regime_of(od, n_stacks, loc["max_diff"]), od["seed_len"], hit_cap=cap)
+    assert int(t["sc"][11]) == 0 and t["hit_cap"] == cap, "reads left unfinished"
+    t = dict(b, **chain.hit_positions64(gi, t, n, max_occ, fill=0x77))
     host = dict(flags=t["flags"].cpu().numpy().astype(np.uint32), hit_off=t["hit_off"].cpu().numpy(),
                 hits=t["hits"].cpu().numpy().view(np.uint32)[:cap * ALN64_WORDS].reshape(-1, ALN64_WORDS),
                 pos_off=t["pos_off"].cpu().numpy(), pos=t["pos"].cpu().numpy().view(U64).reshape(-1, 4),
@@ -132,12 +86,11 @@ def fabricate(lens, codes, rows):
     """A batch made by hand: rows = (read, strand, gap, text position, in-chromosome
     position), in read order; one hit record per row."""
     import torch
-    from hsa_amd._lib import ALN64_WORDS, JOB_DTYPE, pad_codes
+    from hsa_amd.chain import make_jobs
+    from hsa_amd._lib import ALN64_WORDS, pad_codes
     lens = np.asarray(lens, np.uint32)
     n = len(lens)
-    jobs = np.zeros(n, JOB_DTYPE)
-    jobs["off"] = np.concatenate([[0], np.cumsum(lens.astype(np.uint64))[:-1]])
-    jobs["len"] = lens
+    jobs = make_jobs(lens, 0, 0)
     reads = np.array([r[0] for r in rows], np.int64)
     assert (np.diff(reads) >= 0).all()
     cnt = np.bincount(reads, minlength=n)[:n]
@@ -150,7 +103,7 @@ def fabricate(lens, codes, rows):
         hits[k, 1] = strand << 30
         pos[k] = (p, 1, ori, p)
     pos_hit = (np.arange(len(rows)) - pos_off[reads]).astype(np.uint32) if len(rows) else np.zeros(1, np.uint32)
-    t = dict(jobs=dev(jobs.view(np.uint8)), codes=dev(pad_codes(codes)), hit_off=dev(pos_off[:-1].copy()),
+    t = dict(jobs=dev(jobs), codes=dev(pad_codes(codes)), hit_off=dev(pos_off[:-1]),
              hits=dev(hits), pos_off=dev(pos_off), pos=dev(pos), pos_hit=dev(pos_hit),
              pos_ctr=dev(np.array([len(rows), len(rows), 0, 0], np.int64)), n_jobs=n, max_len=int(lens.max()),
              pos_cap=len(rows))

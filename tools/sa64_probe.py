@@ -15,7 +15,6 @@ until a sampled row (not a counter in the kernel).  A walk is a chain of depende
 the rate at the nearest table size, 32 waves per CU, is reported.
 
 One JSON object on stdout (and in --out)."""
-import argparse
 import ctypes as C
 import json
 import os
@@ -26,14 +25,11 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from choose_probe import GENOME_SEED, RECORDS, emit, log, parser, probe_batch, probe_opts, timed_ms  # noqa: E402
 
 GENOME5_T = 15_000_000_003      # bench.py's config 5
-GENOME_SEED = 1234              # bench.py's GENOME_SEED
-RECORDS = 24                    # bench.py's RECORDS
-
-
-def log(*a):
-    print(*a, file=sys.stderr, flush=True)
 
 
 def chain_rate(path, table_bytes):
@@ -54,22 +50,14 @@ def chain_rate(path, table_bytes):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--genome", type=int, default=GENOME5_T, help="text length (default: config 5's 15 Gbp)")
-    ap.add_argument("--interval", type=int, default=32)
-    ap.add_argument("--batch", type=int, default=1_000_000)
-    ap.add_argument("--read-len", type=int, default=250)
+    ap = parser(__doc__, GENOME5_T, "text length (default: config 5's 15 Gbp)", 250)
     ap.add_argument("--max-occ", type=int, nargs="+", default=[1, 50])
-    ap.add_argument("--launches", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--walk-sample", type=int, default=20_000)
     ap.add_argument("--chain-log", default=None, help="output of `tools/gather_probe chain16`")
-    ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
 
-    from hsa_amd import _lib, synth
+    from hsa_amd import _lib, chain, synth
     import torch
-    from hsa_amd._lib import DeviceBatch, GapOpt, HitPosBatch64, Regime
     L = _lib.lib()
     T, s = a.genome, a.interval
     nw = (T + 15) // 16
@@ -98,37 +86,20 @@ def main(argv=None):
     reads, _ = synth.make_reads(genome, recs, a.batch, a.read_len, 8 * 1_000_000, max_mm=4)
     del genome
     log(f"[sa64_probe] {a.batch} reads in {time.time() - t0:.1f} s")
-    opt = GapOpt.default()
-    opt.max_diff, opt.fnr, opt.max_gapo = 4, -1.0, 0
-    opt.mode &= ~0x01
-    n_stacks = (opt.max_diff + 1) * opt.s_mm + (opt.max_gapo + 1) * opt.s_gapo + (opt.max_gape + 1) * opt.s_gape
-    rg = Regime(s_mm=opt.s_mm, s_gapo=opt.s_gapo, s_gape=opt.s_gape, mode=0, indel_end_skip=opt.indel_end_skip,
-                max_del_occ=opt.max_del_occ, max_entries=opt.max_entries, max_gapo=0, max_gape=opt.max_gape,
-                max_seed_diff=opt.max_seed_diff, max_top2=opt.max_top2, n_stacks=n_stacks, max_diff=opt.max_diff)
+    opt = probe_opts(0)
+    rg = chain.local_regime(opt, a.read_len)[2]
     n = a.batch
-    jobs = np.zeros(n, _lib.JOB_DTYPE)
-    jobs["off"] = np.arange(n, dtype=np.uint64) * a.read_len
-    jobs["len"] = a.read_len
-    jobs["max_diff"] = opt.max_diff
-    jobs["seed_len"] = opt.seed_len
-    d_jobs = torch.from_numpy(jobs.view(np.uint8).copy()).cuda()
-    d_codes = torch.from_numpy(_lib.pad_codes(reads.reshape(-1))).cuda()
     hit_cap = n * 8
-    o = dict(n=torch.zeros(n, dtype=torch.int32, device="cuda"), f=torch.zeros(n, dtype=torch.int32, device="cuda"),
-             o=torch.zeros(n, dtype=torch.int64, device="cuda"),
-             h=torch.zeros(hit_cap * _lib.ALN64_WORDS + 2, dtype=torch.int32, device="cuda"),
-             c=torch.zeros(16, dtype=torch.int64, device="cuda"))
-    b = DeviceBatch(d_jobs=d_jobs.data_ptr(), n_jobs=n, d_codes=d_codes.data_ptr(), d_n_aln=o["n"].data_ptr(),
-                    d_flags=o["f"].data_ptr(), d_hit_off=o["o"].data_ptr(), d_hits=o["h"].data_ptr(), hit_cap=hit_cap,
-                    d_counters=o["c"].data_ptr(), max_len=a.read_len, max_seed=opt.seed_len)
+    bt = probe_batch(reads, a.read_len, opt)             # (kept: b holds addresses into its tensors)
+    b, o = chain.search64_batch(bt, 0, n, hit_cap, opt["seed_len"])
     gi.search_device64([rg], b)
     torch.cuda.synchronize()
-    ctr = o["c"].cpu().numpy()
-    log(f"[sa64_probe] searched: {int((o['n'] > 0).sum())} reads with hits, {int(ctr[1])} records, "
+    ctr = o["sc"].cpu().numpy()
+    log(f"[sa64_probe] searched: {int((o['n_aln'] > 0).sum())} reads with hits, {int(ctr[1])} records, "
         f"{int(ctr[11])} unfinished")
 
     res = dict(tool="sa64_probe", text_bp=T, interval=s, batch=n, read_len=a.read_len, options="-n 4 -o 0",
-               reads_with_hits=int((o["n"] > 0).sum()), hit_records=int(ctr[1]), launches=a.launches, warmup=a.warmup,
+               reads_with_hits=int((o["n_aln"] > 0).sum()), hit_records=int(ctr[1]), launches=a.launches, warmup=a.warmup,
                rank_table_bytes=int(T), samples_bytes=int(8 * ((T + s) // s)),
                lf_steps="rows x mean walk of a sample of the rows (hsa_psi_minus_batch64 until a sampled row)", runs=[])
     rng = np.random.default_rng(1)
@@ -137,25 +108,10 @@ def main(argv=None):
     stream = tst.cuda_stream
     assert stream, "need a non-default stream (the library maps NULL to the index's own)"
     for mo in a.max_occ:
-        cap = n * mo
-        po = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
-        p = torch.zeros(cap * 4, dtype=torch.int64, device="cuda")
-        ph = torch.zeros(cap, dtype=torch.int32, device="cuda")
-        c = torch.zeros(4, dtype=torch.int64, device="cuda")
-        hb = HitPosBatch64(d_n_aln=o["n"].data_ptr(), d_hit_off=o["o"].data_ptr(), d_hits=o["h"].data_ptr(), n_jobs=n,
-                           max_occ=mo, d_pos_off=po.data_ptr(), d_pos=p.data_ptr(), d_pos_hit=ph.data_ptr(),
-                           pos_cap=cap, d_counters=c.data_ptr())
+        hb, pos = chain.hit_positions64_batch(o, n, mo)
+        po, ph, c = pos["pos_off"], pos["pos_hit"], pos["pos_ctr"]
         torch.cuda.synchronize()
-        for _ in range(a.warmup):
-            gi.hit_positions64(hb, stream=stream)
-        torch.cuda.synchronize()
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(a.launches + 1)]
-        ev[0].record(tst)
-        for i in range(a.launches):
-            gi.hit_positions64(hb, stream=stream)
-            ev[i + 1].record(tst)
-        torch.cuda.synchronize()
-        ms = np.array([ev[i].elapsed_time(ev[i + 1]) for i in range(a.launches)])
+        ms = timed_ms(lambda: gi.hit_positions64(hb, stream=stream), tst, a.launches, a.warmup)
         cc = c.cpu().numpy()
         rows = int(cc[1])
         # the mean walk of a sample of these rows
@@ -163,8 +119,8 @@ def main(argv=None):
         pick = np.sort(rng.choice(tot, min(a.walk_sample, tot), replace=False))
         off = po.cpu().numpy()
         rd = np.searchsorted(off, pick, side="right") - 1
-        n_aln, hoff = o["n"].cpu().numpy(), o["o"].cpu().numpy()
-        hits = o["h"].cpu().numpy().view(np.uint32)[:hit_cap * _lib.ALN64_WORDS].reshape(-1, _lib.ALN64_WORDS)
+        n_aln, hoff = o["n_aln"].cpu().numpy(), o["hit_off"].cpu().numpy()
+        hits = o["hits"].cpu().numpy().view(np.uint32)[:hit_cap * _lib.ALN64_WORDS].reshape(-1, _lib.ALN64_WORDS)
         phh = ph.cpu().numpy()
         cur = np.zeros(len(pick), np.uint64)
         for j, (t, r) in enumerate(zip(pick, rd)):
@@ -199,15 +155,10 @@ def main(argv=None):
         log(f"[sa64_probe] max_occ {mo}: {rows} rows in {med:.3f} ms, {run['rows_per_s'] / 1e6:.1f} M rows/s, "
             f"mean walk {walk:.1f}, {run['lf_steps_per_s'] / 1e9:.2f} G LF steps/s")
         res["runs"].append(run)
-        del po, p, ph, c
+        del hb, pos, po, ph, c
         torch.cuda.empty_cache()
     gi.close()
-    txt = json.dumps(res, indent=1)
-    print(txt)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(txt + "\n")
-    return 0
+    return emit(res, a.out)
 
 
 if __name__ == "__main__":
