@@ -39,7 +39,8 @@ EXPORTS = [  # every symbol include/hsa_gpu.h and include/hsa_bwtaln.h declare
     "hsa_index_set_text64_device", "hsa_refine_rows_device64", "hsa_choose_hits_device64",
     "hsa_choose_timing", "hsa_choose_launch_times", "hsa_sam_lines_device64", "hsa_sam_timing",
     "hsa_sam_launch_times", "hsa_index_levels", "hsa_reads_device", "hsa_reads_timing",
-    "hsa_reads_launch_times",
+    "hsa_reads_launch_times", "hsa_fasta_scratch_bytes", "hsa_fasta_device", "hsa_bwt_files_scratch_bytes",
+    "hsa_bwt_files_device", "hsa_fasta_timing", "hsa_fasta_launch_times", "hsa_bwt_files_launch_times",
 ]
 SP_RES_WORDS = 20  # hsa_splice_match_batch's per-read answer (include/hsa_gpu.h)
 ALN64_WORDS = 14   # hsa_aln64_t (include/hsa_gpu.h)
@@ -63,6 +64,14 @@ HSA_RD_TILE = 4096
 RD_COUNTERS = ("seen", "loaded", "jobs_wanted", "jobs_written", "code_wanted", "code_written", "name_wanted",
                "name_written", "qual_wanted", "qual_written", "consumed", "bad_record", "bad_offset", "max_loaded",
                "max_kept", "threshold")
+# hsa_fasta_device: words per record row, the counters, the zero words behind a text
+FA_REC_WORDS = 4
+FA_COUNTERS = ("seen", "kept", "rec_written", "blocks", "blk_written", "characters", "total", "T", "rev_T",
+               "pac_wanted", "pac_written", "rpac_wanted", "rpac_written", "text_wanted", "text_written",
+               "rtext_wanted", "rtext_written", "refused")
+FA_PAD_WORDS = 8
+FA_LAUNCHES = ("marks", "marks_scan", "spans", "span_scans", "count", "count_scan", "pack", "reverse")
+BF_LAUNCHES = ("blocks", "scan", "samples")
 
 
 class HsaError(RuntimeError):
@@ -204,6 +213,17 @@ class ReadsBatch(C.Structure):
                 ("job_cap", C.c_uint64), ("d_codes", C.c_void_p), ("code_cap", C.c_uint64), ("d_names", C.c_void_p),
                 ("name_cap", C.c_uint64), ("d_name_off", C.c_void_p), ("d_quals", C.c_void_p), ("qual_cap", C.c_uint64),
                 ("d_qual_off", C.c_void_p), ("d_rec", C.c_void_p), ("d_counters", C.c_void_p)]
+
+
+class FastaBatch(C.Structure):
+    """hsa_fasta_batch_t (include/hsa_gpu.h): the bytes of a FASTA in; the .pac and .rev.pac
+    bytes, the two texts, the record and block tables and the counters out, each with its
+    capacity; the caller's scratch.  All device pointers."""
+    _fields_ = [("d_in", C.c_void_p), ("n_in", C.c_uint64), ("d_pac", C.c_void_p), ("pac_cap", C.c_uint64),
+                ("d_rpac", C.c_void_p), ("rpac_cap", C.c_uint64), ("d_text", C.c_void_p), ("text_cap", C.c_uint64),
+                ("d_rtext", C.c_void_p), ("rtext_cap", C.c_uint64), ("d_rec", C.c_void_p), ("rec_cap", C.c_uint64),
+                ("d_blk", C.c_void_p), ("blk_cap", C.c_uint64), ("d_counters", C.c_void_p),
+                ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_uint64)]
 
 
 def log_n_table() -> np.ndarray:
@@ -369,6 +389,15 @@ def lib():
         L.hsa_reads_timing.argtypes = [C.c_int]
         L.hsa_reads_timing.restype = None
         L.hsa_reads_launch_times.argtypes = [vp, f32]
+    if hasattr(L, "hsa_fasta_device"):              # (older A/B builds lack the FASTA loader)
+        L.hsa_fasta_scratch_bytes.argtypes = [C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.hsa_fasta_device.argtypes = [C.c_int, C.POINTER(FastaBatch), vp]
+        L.hsa_bwt_files_scratch_bytes.argtypes = [C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.hsa_bwt_files_device.argtypes = [C.c_int, C.c_uint64, vp, vp, vp, vp, vp, C.c_uint64, vp]
+        L.hsa_fasta_timing.argtypes = [C.c_int]
+        L.hsa_fasta_timing.restype = None
+        L.hsa_fasta_launch_times.argtypes = [f32]
+        L.hsa_bwt_files_launch_times.argtypes = [f32]
     if hasattr(L, "hsa_extend_batch"):
         L.hsa_extend_batch.argtypes = [vp, C.POINTER(Regime), C.c_int, vp, C.c_int, u8, i32, C.c_size_t, i32, i32,
                                        u32]

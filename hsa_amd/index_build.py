@@ -1,6 +1,9 @@
 """From-scratch 2BWT index builder: a FASTA file -> every file `HSA index` writes
-(`.pac .ann .rev.pac .bwt .fmv .rev.bwt .rev.fmv .sa`), byte-identical, with the
-suffix sorting on the GPU.
+(`.pac .ann .rev.pac .bwt .fmv .rev.bwt .rev.fmv .sa`), byte-identical, on the GPU
+(SURVEY §8f #3): FASTA parsing and packing (hsa_fasta_device), the suffix sorts, and the
+.bwt / .fmv bodies (hsa_bwt_files_device).  The functions below are the host restatement of
+the stages around the sorts: build_index(host=True) runs them, and the device stages are
+tested against them.
 
 The reference builds its BWTs with an incremental CPU construction
 (BWTIncConstructFromPacked, BWTConstruct.c:108; hours at hg19 size) and its sampled
@@ -221,29 +224,132 @@ def write_sa(prefix: str, T: int, isa0: int, Cc: np.ndarray, interval: int, sa: 
 
 
 def build_index(fasta: str, prefix: str | None = None, device: int = 0, sa_interval: int = SA_INTERVAL,
-                seed: int = 0) -> dict:
+                seed: int = 0, host: bool = False, times: dict | None = None) -> dict:
     """Write every `HSA index` file of `fasta` under `prefix` (default: the FASTA path):
-    prefix.index.{pac,ann,rev.pac,bwt,fmv,rev.bwt,rev.fmv,sa}.  Returns the lengths."""
+    prefix.index.{pac,ann,rev.pac,bwt,fmv,rev.bwt,rev.fmv,sa}.  Returns the lengths.
+
+    The FASTA's bytes go to the device once; parsing, packing, both texts, the sorts and the
+    .bwt / .fmv bodies are made there (hsa_fasta_device, hsa_build_bwt_index_device,
+    hsa_bwt_files_device) and only file-ready bytes and the two annotation tables come back.
+    host=True keeps parsing, packing and the file bodies on the host (the functions above
+    and index_io's: the restatement the device path is tested against); the files are the
+    same.  `times`, when given, receives the seconds per stage: parse (FASTA to both texts),
+    sort (the two suffix sorts), bodies (.bwt / .fmv bodies), write (the files)."""
     prefix = prefix or fasta
+    tm = _Stages(times)
+    if host:
+        return _build_index_host(fasta, prefix, device, sa_interval, seed, tm)
+    return _build_index_device(fasta, prefix, device, sa_interval, seed, tm)
+
+
+class _Stages:
+    """Seconds per stage of a build, summed into `times` (a stage may come more than once)."""
+
+    def __init__(self, times):
+        import time
+        self.times, self.clock, self.t0 = times, time.perf_counter, time.perf_counter()
+
+    def done(self, stage: str, sync: bool = True) -> None:
+        if self.times is None:
+            return
+        if sync:
+            import torch
+            torch.cuda.synchronize()
+        t = self.clock()
+        self.times[stage] = self.times.get(stage, 0.0) + t - self.t0
+        self.t0 = t
+
+
+def _build_index_host(fasta, prefix, device, sa_interval, seed, tm):
     with open(fasta, "rb") as f:
         data = f.read()
     codes, ann, total = parse_fasta(data)
     pac = pac_bytes(codes, total)
     rpac = reverse_pac(pac)
+    text = pac_text(pac)
+    rtext = pac_text(rpac)
+    tm.done("parse", sync=False)
     with open(f"{prefix}.index.pac", "wb") as f:
         f.write(pac)
     with open(f"{prefix}.index.rev.pac", "wb") as f:
         f.write(rpac)
     with open(f"{prefix}.index.ann", "w") as f:
         f.write(ann_text(ann, total, seed))
-    text = pac_text(pac)
+    tm.done("write", sync=False)
+    # (_device_bwt packs the text for the device and unpacks the BWT: host work around the sort)
     bwt, isa0, Cc, sa = _device_bwt(text, sa_interval, device)
-    index_io.write_bwt_files(prefix, len(text), isa0, Cc, bwt)
-    write_sa(prefix, len(text), isa0, Cc, sa_interval, sa)
-    rtext = pac_text(rpac)
     rbwt, risa0, rCc, _ = _device_bwt(rtext, 0, device)
-    index_io.write_bwt_files(prefix, len(rtext), risa0, rCc, rbwt, suffix=".rev")
+    tm.done("sort")
+    bodies = [(index_io.pack_codes_msb(b), *index_io.occ_files(b)) for b in (bwt, rbwt)]
+    tm.done("bodies", sync=False)
+    for suffix, T, i0, cc, body in (("", len(text), isa0, Cc, bodies[0]), (".rev", len(rtext), risa0, rCc, bodies[1])):
+        _write_bwt_bodies(prefix, suffix, i0, cc, *body)
+    write_sa(prefix, len(text), isa0, Cc, sa_interval, sa)
+    tm.done("write", sync=False)
     return {"T": len(text), "rev_T": len(rtext), "records": len(ann), "characters": total}
+
+
+def _write_bwt_bodies(prefix, suffix, isa0, Cc, msb, minor, major) -> None:
+    """prefix.index{suffix}.bwt and .fmv from their bodies (index_io.write_bwt_files' format)."""
+    head = np.concatenate([[isa0], np.asarray(Cc, np.uint32)[1:5]]).astype(np.uint32)
+    with open(f"{prefix}.index{suffix}.bwt", "wb") as f:
+        f.write(head.tobytes())
+        f.write(msb.tobytes())
+    with open(f"{prefix}.index{suffix}.fmv", "wb") as f:
+        f.write(head.tobytes())
+        f.write(minor.tobytes())
+        f.write(major.tobytes())
+
+
+def _build_index_device(fasta, prefix, device, sa_interval, seed, tm):
+    import torch
+    from . import fasta as fa
+    from ._lib import check, lib
+    n_in = os.path.getsize(fasta)
+    if n_in >= fa.MAX_INPUT:
+        raise ValueError(f"{fasta}: {n_in} bytes; this builder reads a FASTA under 2^32 - 256 bytes "
+                         "(the .ann and .sa formats are 32-bit)")
+    data = np.fromfile(fasta, np.uint8)
+    with torch.cuda.device(device):
+        d_in = torch.from_numpy(data).cuda()
+        p = fa.parse_device(d_in, len(data), device)
+        del d_in
+        if p.refused is not None:
+            what = ("does not begin with '>'" if p.refused == 0 and data[:1].tobytes() != b">" else
+                    "has a '>' inside a header line, or a last header line without a newline,")
+            raise ValueError(f"{fasta}: the FASTA {what} at byte {p.refused}: not answered")
+        c = p.counters
+        T, rT = c["T"], c["rev_T"]
+        if T < 1 or rT < 1:
+            raise ValueError(f"{fasta}: a text of {T} characters ({rT} reversed) is too short for an index")
+        tm.done("parse")
+        files = [("pac", p.pac.cpu().numpy().tobytes()), ("rev.pac", p.rpac.cpu().numpy().tobytes())]
+        ann = ann_text(fa.ann_rows(data, p.rec, p.blk), c["total"], seed).encode()
+        files.append(("ann", ann))
+        for ext, body in files:
+            with open(f"{prefix}.index.{ext}", "wb") as f:
+                f.write(body)
+        tm.done("write")
+        built = []
+        for text, n, interval in ((p.text, T, sa_interval), (p.rtext, rT, 0)):
+            out = torch.zeros((n + 15) // 16 + 8, dtype=torch.int32, device="cuda")
+            isa0 = C.c_uint64()
+            Cc = np.zeros(5, np.uint64)
+            ns = (n + interval) // interval if interval else 0
+            sa = torch.zeros(max(ns, 1), dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            check(lib().hsa_build_bwt_index_device(device, n, text.data_ptr(), out.data_ptr(), C.byref(isa0), Cc,
+                                                   interval, sa.data_ptr() if ns else None))
+            built.append((out, n, int(isa0.value), Cc.astype(np.uint32), sa[:ns] if ns else None))
+        tm.done("sort")
+        bodies = [fa.bwt_files_device(out, n, device) for out, n, _, _, _ in built]
+        tm.done("bodies")
+        for suffix, (_, n, isa0, Cc, sa), body in zip(("", ".rev"), built, bodies):
+            _write_bwt_bodies(prefix, suffix, isa0, Cc, *(t.cpu().numpy() for t in body))
+            if sa is not None:
+                write_sa(prefix, n, isa0, Cc, sa_interval, sa.cpu().numpy().view(np.uint32))
+        tm.done("write")
+    return {"T": T, "rev_T": rT, "records": c["kept"], "characters": c["total"]}
 
 
 def main(argv=None):
@@ -254,8 +360,10 @@ def main(argv=None):
     ap.add_argument("--prefix", default=None)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--sa-interval", type=int, default=SA_INTERVAL)
+    ap.add_argument("--host", action="store_true", help="parse, pack and make the .bwt/.fmv bodies on the host "
+                                                        "(only the suffix sorts on the GPU); the files are the same")
     a = ap.parse_args(argv)
-    print(build_index(a.fasta, a.prefix, a.device, a.sa_interval))
+    print(build_index(a.fasta, a.prefix, a.device, a.sa_interval, host=a.host))
 
 
 if __name__ == "__main__":

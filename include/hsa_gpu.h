@@ -904,6 +904,94 @@ int hsa_reads_device(hsa_index_t *ix, const hsa_reads_batch_t *b, void *stream);
 void hsa_reads_timing(int on);
 int hsa_reads_launch_times(hsa_index_t *ix, float *ms);
 
+/* ---- FASTA bytes to the packed texts and the annotation tables ----
+ * HSPParseFASTAToPacked (HSP.c:180-343) and BuildReversePacked (2BWT-Builder.c:116-213) for
+ * a whole FASTA whose bytes sit in device memory, with the grammar of
+ * hsa_amd/index_build.py (_records, parse_fasta): a '>' starts a record; the name runs to
+ * the first tab, space or newline, at most 256 bytes; the rest of the header line is
+ * skipped; every later byte except '\n' up to the next '>' is sequence, a-z as A-Z; only A,
+ * C, G, T are unambiguous ('\r' is not).  Records under 75 sequence bytes are dropped.  In a
+ * kept record a run of fewer than 10 ambiguous bytes becomes 'G' and a longer one is
+ * dropped: at the record's start it shifts the first block's ori, at its end it is cut,
+ * inside it closes a block and opens the next; ori is the number within the record (the
+ * ambiguous bytes counted, the newlines not) of the block's first character; an
+ * all-ambiguous record keeps one block with end = start - 1; `total` sums the kept records'
+ * lengths with their ambiguous bytes.
+ *
+ * Takes a device number, as the builders do: the call comes before any index exists.  With
+ * no handle to grow scratch on, the caller passes d_scratch (256-byte aligned, at least
+ * hsa_fasta_scratch_bytes(n_in): about 4 % of the input, nothing per byte).  Launches on
+ * `stream` (NULL: the device's null stream) and does not synchronise; no host round trip
+ * between the launches; output positions come from scans, never from atomics, so two runs
+ * give equal arrays.
+ *
+ * Refused, not answered (the call still returns 0, [17] holds the lowest such offset and
+ * the other outputs are of no use): a '>' inside a header line (its offset: the reference
+ * skips to the line's end, _records starts a record), a last header line with no '\n'
+ * before the end of the input (the offset of its '>'), an input that does not begin with
+ * '>' (0).  Everything else parse_fasta accepts is answered exactly.
+ *
+ * Outputs (each with a capacity; no byte at or past a capacity is touched):
+ *   d_pac    the .pac bytes (pac_bytes): 4 codes per byte, first in the high bits, a 0 byte
+ *            when total % 4 == 0, the byte total % 4.  4-byte aligned.
+ *   d_rpac   the .rev.pac bytes (reverse_pac): the forward text reversed, 1 to 4 bytes for a
+ *            partial last word, a full last word lost when T % 16 == 0, the .pac's length
+ *            byte.  4-byte aligned.
+ *   d_text   the forward text as hsa_build_bwt_index_device takes it: LSB-first words of
+ *            T = (.pac bytes - 2) * 4 + last byte characters (shorter than the kept characters
+ *            or longer by up to three 'A's), then 8 zero words.  Capacity in words.
+ *   d_rtext  the same for the .rev.pac's text of rT characters.
+ *   d_rec    HSA_FA_REC_WORDS u32 per kept record: the name's offset in the input, its
+ *            length, L, the record's first block.  Capacity in rows.
+ *   d_blk    four u32 per block, in file order: kept record, start, end, ori.  Rows.
+ * d_counters (HSA_FA_COUNTERS u64): [0] records seen, [1] kept (rows wanted), [2] rows
+ * written, [3] blocks wanted, [4] written, [5] kept characters, [6] total, [7] T, [8] rT,
+ * [9] .pac bytes wanted, [10] written, [11] .rev.pac bytes wanted, [12] written, [13] text
+ * words wanted (the padding included), [14] written, [15] reversed text words wanted, [16]
+ * written, [17] the refused offset (all-ones: none).  wanted > written: run again with
+ * more room (a reversed text made from a forward text that was cut is of no use either).
+ * An input without a kept unambiguous character has T = 0 (the host's pac_text fails on it).
+ * Null pointers, a short scratch and n_in >= 2^32 - 256 are HSA_E_ARG. */
+#define HSA_FA_REC_WORDS 4
+#define HSA_FA_COUNTERS 18
+typedef struct {
+    const uint8_t *d_in; uint64_t n_in;
+    uint8_t *d_pac; uint64_t pac_cap;
+    uint8_t *d_rpac; uint64_t rpac_cap;
+    uint32_t *d_text; uint64_t text_cap;
+    uint32_t *d_rtext; uint64_t rtext_cap;
+    uint32_t *d_rec; uint64_t rec_cap;
+    uint32_t *d_blk; uint64_t blk_cap;
+    uint64_t *d_counters;
+    void *d_scratch; uint64_t scratch_bytes;
+} hsa_fasta_batch_t;
+int hsa_fasta_scratch_bytes(int device, uint64_t n_in, uint64_t *bytes);
+int hsa_fasta_device(int device, const hsa_fasta_batch_t *b, void *stream);
+
+/* The bodies of a .bwt and a .fmv file from the builder's output (d_bwt_lsb: the $-less BWT,
+ * LSB-first, ceil(T/16) words; 1 <= T < 2^32 - 1): d_bwt_msb, ceil(T/16) words of 16 codes,
+ * the first in the top bits, the tail past T cleared (index_io.pack_codes_msb); d_minor,
+ * ((n_occ + 1) / 2) * 4 words, and d_major, ((n_occ + 255) / 256) * 4 words, exactly as
+ * index_io.occ_files makes them: n_occ = (T + 255) / 256 + 1 samples, the zero padding past
+ * T counted as 'A', 16-bit halves with the even sample in the high half, the last sample
+ * repeated in the unread low half when n_occ is odd, a major sample every 65 536
+ * characters.  d_scratch: 256-byte aligned, hsa_bwt_files_scratch_bytes(T).  Launches on
+ * `stream`, does not synchronise. */
+int hsa_bwt_files_scratch_bytes(int device, uint64_t T, uint64_t *bytes);
+int hsa_bwt_files_device(int device, uint64_t T, const uint32_t *d_bwt_lsb, uint32_t *d_bwt_msb,
+                         uint32_t *d_minor, uint32_t *d_major, void *d_scratch, uint64_t scratch_bytes,
+                         void *stream);
+/* Probes: with hsa_fasta_timing(1) both calls record events around their launches; the
+ * times in ms of the last timed call (waits for it).  hsa_fasta_device: k_fa_marks (with
+ * the memsets), the marks' scan, k_fa_spans, the two span scans, k_fa_count, the count scan,
+ * k_fa_pack with k_fa_finish, k_fa_reverse.  hsa_bwt_files_device: k_bf_blocks, the scan,
+ * k_bf_samples. */
+#define HSA_FA_LAUNCHES 8
+#define HSA_BF_LAUNCHES 3
+void hsa_fasta_timing(int on);
+int hsa_fasta_launch_times(float *ms);
+int hsa_bwt_files_launch_times(float *ms);
+
 #ifdef __cplusplus
 }
 #endif
