@@ -37,7 +37,7 @@ EXPORTS = [  # every symbol include/hsa_gpu.h and include/hsa_bwtaln.h declare
     "hsa_splice_device", "hsa_build_bwt_index_device64", "hsa_index_set_sa64", "hsa_index_set_sa64_device",
     "hsa_sa_position_batch64", "hsa_sa_position_device64", "hsa_psi_minus_batch64", "hsa_hit_positions_device64",
     "hsa_index_set_text64_device", "hsa_refine_rows_device64", "hsa_choose_hits_device64",
-    "hsa_choose_timing", "hsa_choose_launch_times", "hsa_sam_lines_device64", "hsa_sam_timing",
+    "hsa_choose_timing", "hsa_choose_launch_times", "hsa_sam_lines_device64", "hsa_sam_timing", "hsa_splice_lines_device", "hsa_sam_merge_device",
     "hsa_sam_launch_times", "hsa_index_levels", "hsa_reads_device", "hsa_reads_timing",
     "hsa_reads_launch_times", "hsa_fasta_scratch_bytes", "hsa_fasta_device", "hsa_bwt_files_scratch_bytes",
     "hsa_bwt_files_device", "hsa_fasta_timing", "hsa_fasta_launch_times", "hsa_bwt_files_launch_times",
@@ -55,6 +55,11 @@ CHOOSE_NONE, CHOOSE_UNIQUE, CHOOSE_REPEAT = range(3)
 # hsa_sam_lines_device64: per-read status, the longest line a batch may declare
 HSA_SAM_OK, HSA_SAM_NOHIT, HSA_SAM_ROWS, HSA_SAM_REFINE, HSA_SAM_INPUT = range(5)
 HSA_SAM_MAX_LINE = 61440
+# hsa_splice_lines_device: per-read status, words per read row, the most score buckets of hsa_splice_device
+(HSA_SL_OK, HSA_SL_NONE, HSA_SL_HANDED, HSA_SL_NOPAIR, HSA_SL_MULTI, HSA_SL_REFINE, HSA_SL_POS, HSA_SL_INTRON,
+ HSA_SL_INPUT) = range(9)
+SL_ROW_WORDS = 24
+HSA_SP_MAX_STACKS = 128
 # hsa_reads_device: per-record status, words per record row, the longest read, the bytes of
 # the input per block of the newline passes, the counters
 HSA_RD_SEARCHED, HSA_RD_NDROP, HSA_RD_POLYAT = range(3)
@@ -200,6 +205,27 @@ class SamBatch64(C.Structure):
                 ("d_chr_names", C.c_void_p), ("d_chr_off", C.c_void_p), ("n_chr", C.c_uint32), ("flag", C.c_uint32),
                 ("max_top2", C.c_int32), ("comp_read", C.c_int32), ("max_line", C.c_uint32), ("d_line_off", C.c_void_p),
                 ("d_out", C.c_void_p), ("out_cap", C.c_uint64), ("d_line_stat", C.c_void_p), ("d_counters", C.c_void_p)]
+
+
+class SpliceLinesBatch(C.Structure):
+    """hsa_splice_lines_batch_t (include/hsa_gpu.h): the batch, hsa_splice_device's results and
+    the reads' names and qualities in; the spliced reads' SAM text, its per-read offsets,
+    statuses and row words out, all device pointers."""
+    _fields_ = [("d_jobs", C.c_void_p), ("n_jobs", C.c_int), ("d_codes", C.c_void_p), ("d_flags", C.c_void_p),
+                ("d_n_aln", C.c_void_p), ("d_res", C.c_void_p), ("d_names", C.c_void_p), ("d_name_off", C.c_void_p),
+                ("d_quals", C.c_void_p), ("d_qual_off", C.c_void_p), ("d_chr_names", C.c_void_p), ("d_chr_off", C.c_void_p),
+                ("n_chr", C.c_uint32), ("flag", C.c_uint32), ("max_top2", C.c_int32), ("comp_read", C.c_int32),
+                ("max_len", C.c_int32), ("max_line", C.c_uint32), ("cigar_stride", C.c_uint32), ("pad", C.c_uint32),
+                ("d_rows", C.c_void_p), ("d_cigar", C.c_void_p), ("d_line_off", C.c_void_p), ("d_out", C.c_void_p),
+                ("out_cap", C.c_uint64), ("d_line_stat", C.c_void_p), ("d_counters", C.c_void_p)]
+
+
+class SamMergeBatch(C.Structure):
+    """hsa_sam_merge_batch_t (include/hsa_gpu.h): two writers' texts and offsets over the same
+    reads in, one text in read order out, all device pointers."""
+    _fields_ = [("n_jobs", C.c_int), ("d_line_off_a", C.c_void_p), ("d_text_a", C.c_void_p), ("text_a_len", C.c_uint64),
+                ("d_line_off_b", C.c_void_p), ("d_text_b", C.c_void_p), ("text_b_len", C.c_uint64), ("d_line_off", C.c_void_p),
+                ("d_out", C.c_void_p), ("out_cap", C.c_uint64), ("d_counters", C.c_void_p)]
 
 
 class ReadsBatch(C.Structure):
@@ -382,6 +408,9 @@ def lib():
     if hasattr(L, "hsa_sam_lines_device64"):        # (older A/B builds lack the SAM lines)
         L.hsa_sam_lines_device64.argtypes = [vp, C.POINTER(SamBatch64), vp]
         L.hsa_sam_timing.argtypes = [C.c_int]
+    if hasattr(L, "hsa_splice_lines_device"):
+        L.hsa_splice_lines_device.argtypes = [vp, C.POINTER(SpliceLinesBatch), vp]
+        L.hsa_sam_merge_device.argtypes = [vp, C.POINTER(SamMergeBatch), vp]
         L.hsa_sam_timing.restype = None
         L.hsa_sam_launch_times.argtypes = [vp, f32]
     if hasattr(L, "hsa_reads_device"):              # (older A/B builds lack the FASTQ loader)
@@ -773,6 +802,23 @@ class GpuIndex:
         if not hasattr(lib(), "hsa_sam_lines_device64"):
             raise HsaError("this libhsa_gpu.so has no hsa_sam_lines_device64: rebuild it")
         check(lib().hsa_sam_lines_device64(getattr(self, "h", None), C.byref(batch), stream))
+
+    def splice_lines(self, batch: "SpliceLinesBatch", stream=None):
+        """hsa_splice_lines_device: the SAM lines of the spliced reads of a batch from
+        splice_device's results (batch.d_rows, d_cigar, d_line_off, d_out, d_line_stat,
+        d_counters) on `stream` (a hipStream_t address; None: the index's own); does not
+        synchronise.  hsa_amd.chain.splice_lines drives it."""
+        if not hasattr(lib(), "hsa_splice_lines_device"):
+            raise HsaError("this libhsa_gpu.so has no hsa_splice_lines_device: rebuild it")
+        check(lib().hsa_splice_lines_device(getattr(self, "h", None), C.byref(batch), stream))
+
+    def sam_merge(self, batch: "SamMergeBatch", stream=None):
+        """hsa_sam_merge_device: the lines of sam_lines64 and of splice_lines over the same
+        reads as one text in read order (batch.d_line_off, d_out, d_counters) on `stream`; does
+        not synchronise."""
+        if not hasattr(lib(), "hsa_sam_merge_device"):
+            raise HsaError("this libhsa_gpu.so has no hsa_sam_merge_device: rebuild it")
+        check(lib().hsa_sam_merge_device(getattr(self, "h", None), C.byref(batch), stream))
 
     def reads_device(self, batch: "ReadsBatch", stream=None):
         """hsa_reads_device: the bytes of a FASTQ chunk on the device to a search batch, the

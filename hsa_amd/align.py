@@ -21,11 +21,30 @@ opt->seed_len turns to 0x7fffffff for good at the first searched read, up to the
 is not longer than it (bwtaln.c:332 writes through aux->opt).
 
 Contract.  One line per read with a main-search hit, in read order, byte for byte
-bwa_print_sam1's (bwtse.c:698-799).  A read without one gets no line: the reference sends
-it to bwt_splice_match, for which the 64-bit path has no counterpart; such reads are counted
-and, with --unaligned FILE, written back out as FASTQ.  The text equals the reference's up
-to the first read whose line the reference prints from its splice path, because that read's
-drand48 draws are not seen here (tests/test_gpu_choose.py documents the condition).  No @SQ
+bwa_print_sam1's (bwtse.c:698-799).  A read without one goes to bwt_splice_match in the
+reference.  Without --splice (splice=False, the default) it gets no line; such reads are
+counted and, with --unaligned FILE, written back out as FASTQ, and the text equals the
+reference's up to the first read whose line the reference prints from its splice path,
+because that read's drand48 draws are not seen here (tests/test_gpu_choose.py documents the
+condition).
+
+With --splice (splice=True; an index under 2^32 characters and at most HSA_SP_MAX_STACKS
+score buckets, ValueError otherwise) every such read goes through hsa_splice_device
+(chain.splice32) with the batch's local options, the first one with local_opt.max_diff as
+the batch has it (bwtaln.c:331 wrote that read's own through the caller's block).  A result
+that is not two records of type BWA_TYPE_SPLICING is appended to the read's hit list on the
+device and is chosen, refined and printed like any other (its draws are made in read
+order); a spliced result is paired, refined and printed by hsa_splice_lines_device
+(chain.splice_lines: XT:A:S, CIGAR with an N), and the two writers' lines are merged in
+read order.  Then every line the reference prints is printed, except for reads the device
+refuses, each of which gets no line (exact or nothing), counts towards no_line and goes to
+--unaligned: `handed_back` (hsa_splice_device's status > 0: there is no host
+bwt_splice_match here), `spliced_multi` (more than one pair: the reference's XA format for
+them is not built), `spliced_refused` (a segment's alignment not answered, a position in
+no chromosome block, an N length that is not positive, a line past the bound).  After a
+handed-back read that the reference would have printed as U / R the generator state is no
+longer the reference's, and R reads after it may choose differently; the committed
+fixtures have no such read (0 of 601, 614 and 203 reads sent are handed back).  No @SQ
 header unless --header is given; with it, "@SQ\\tSN:<name>\\tLN:<length>" per chromosome of the
 .ann file, the reference's format (bwt_print_sam_SQ, bwtse.c:826-834).
 
@@ -42,8 +61,8 @@ import sys
 import numpy as np
 
 from . import chain, index_io, reads, sam
-from ._lib import (DRAND48_SEED0, HSA_RD_NDROP, HSA_RD_POLYAT, HSA_RD_SEARCHED, HSA_RF_MAX_LEN, JOB_DTYPE, GapOpt, GpuIndex,
-                   regime_of)
+from ._lib import (ALN64_WORDS, DRAND48_SEED0, HSA_RD_NDROP, HSA_RD_POLYAT, HSA_RD_SEARCHED, HSA_RF_MAX_LEN, HSA_SP_MAX_STACKS,
+                   JOB_DTYPE, SP_RES_WORDS, GapOpt, GpuIndex, regime_of)
 
 HSA_DRAND48_SEED0 = DRAND48_SEED0
 BATCH_READS = 0x186A0            # bwtaln.c:477
@@ -51,6 +70,7 @@ MODE_GAPE, MODE_COMPREAD, MODE_LOGGAP, MODE_NONSTOP = 0x01, 0x02, 0x04, 0x10
 SEED_NONE = reads.SEED_NONE
 TABLE_LEN = HSA_RF_MAX_LEN + 1   # reads past it go through the host parser (and are not refined)
 ONES = 0xFFFFFFFFFFFFFFFF
+TYPE_SPLICING = 4                # bwtaln.h:13
 OPTSTRING = "n:o:e:i:d:l:k:cLR:m:t:NM:O:E:q:f:b012IYB:"       # bwtaln.c:539
 
 
@@ -86,7 +106,7 @@ def parse_options(args):
     o = default_opts()
     extra = dict(header=False, unaligned=None, out=None)
     opte = -1
-    optlist, rest = getopt.gnu_getopt(list(args), OPTSTRING, ["header", "unaligned="])
+    optlist, rest = getopt.gnu_getopt(list(args), OPTSTRING, ["header", "unaligned=", "splice"])
     plain = {"-o": "max_gapo", "-M": "s_mm", "-O": "s_gapo", "-E": "s_gape", "-d": "max_del_occ", "-i": "indel_end_skip",
              "-l": "seed_len", "-k": "max_seed_diff", "-m": "max_entries", "-t": "n_threads", "-R": "max_top2"}
     for k, v in optlist:
@@ -112,6 +132,8 @@ def parse_options(args):
             extra["header"] = True
         elif k == "--unaligned":
             extra["unaligned"] = v
+        elif k == "--splice":
+            extra["splice"] = True                          # (the key is there only when the option is)
         else:
             raise ValueError(f"option {k} is not built (barcodes, Casava filter, Illumina-1.3 qualities, BAM, colour space)")
     if opte > 0:
@@ -331,13 +353,73 @@ def _runs(flags, first, end):
     return out if end > first else []
 
 
-def _run_batch(gi, chr_names, b, opt, out, state, stats):
+def _splice_hits(t, s, first, cnt, stats):
+    """The search tensors t with the unspliced results of the splice search s appended as
+    hits, for jobs [first, first + cnt): a result that is not two records of type
+    BWA_TYPE_SPLICING goes through bwt_aln2seq_core like a main-search hit (bwtse.c:901-907).
+    Its bwt_aln1_t records (9 words) become hsa_aln64_t records (14 words) behind the
+    search's own, two slots per read, and the read's n_aln and hit_off point at them; all on
+    the device.  t itself is left as it is (the lines stage reads the search's n_aln)."""
+    import torch
+    k, ks = first - t["first"], first - s["sp_first"]
+    r = s["res"][ks * SP_RES_WORDS:(ks + cnt) * SP_RES_WORDS].view(cnt, SP_RES_WORDS)
+    sent = ((s["sp_flags"][ks:ks + cnt] & 1) != 0) & (s["sp_n_aln"][ks:ks + cnt] == 0)
+    spliced = (r[:, 1] == 2) & ((r[:, 7] & 0x3FFFFFFF) == TYPE_SPLICING)
+    idx = torch.nonzero(sent & (r[:, 0] == 0) & (r[:, 1] >= 1) & (r[:, 1] <= 2) & ~spliced).view(-1)
+    if idx.numel() == 0:
+        return t
+    rec = r[idx, 2:].reshape(-1, 2, 9)
+    w = torch.zeros((idx.numel(), 2, ALN64_WORDS), dtype=torch.int32, device="cuda")
+    for dst, src in ((0, 0), (1, 5), (2, 1), (4, 2), (6, 3), (8, 4), (10, 6), (11, 7), (12, 8)):
+        w[:, :, dst] = rec[:, :, src]                       # (k, l, rev_k, rev_l: the low words; the high ones are 0)
+    cap = t["hit_cap"]
+    n_aln, hit_off = t["n_aln"].clone(), t["hit_off"].clone()
+    n_aln[k + idx] = r[idx, 1]
+    hit_off[k + idx] = cap + 2 * torch.arange(idx.numel(), device="cuda")
+    stats["spliced_unspliced"] += int(idx.numel())
+    return dict(t, n_aln=n_aln, hit_off=hit_off, hit_cap=cap + 2 * idx.numel(),
+                hits=torch.cat([t["hits"][:cap * ALN64_WORDS], w.view(-1), t["hits"][cap * ALN64_WORDS:]]))
+
+
+def _splice_lines(gi, b, s, first, cnt, chrs, has_qual, opt, stats):
+    """hsa_splice_lines_device over jobs [first, first + cnt): (its output tensors, the bytes
+    of its text, line_stat on the host, the names of the reads it refused)."""
+    import torch
+    from ._lib import HSA_SL_NONE, HSA_SL_NOPAIR, HSA_SL_OK
+    strings = dict(names=b["names"], name_off=b["name_off"][first:], chrs=chrs["chrs"], chr_off=chrs["chr_off"])
+    if has_qual:
+        strings.update(quals=b["quals"], qual_off=b["qual_off"][first:])
+    noff = b["name_off"][first:first + cnt + 1].cpu().numpy().view(np.uint64)
+    max_name = int(np.diff(noff.astype(np.int64)).max()) if cnt else 0
+    stride = 33                                             # two segments' ops and the N
+    max_line = max(1, sam.line_bound(max_name, b["max_len"], chrs["max_chr"], stride, 0, 0))
+    ks = first - s["sp_first"]
+    n_two = int((s["res"][ks * SP_RES_WORDS:(ks + cnt) * SP_RES_WORDS].view(cnt, SP_RES_WORDS)[:, 1] == 2).sum())
+    cap = n_two * (max_name + 2 * b["max_len"] + chrs["max_chr"] + 200) + 64
+    o, ctr = chain.splice_lines(gi, b, s, first, cnt, strings, chrs["n"], max_line, cap, cigar_stride=stride,
+                                max_top2=opt["max_top2"], comp_read=bool(opt["mode"] & MODE_COMPREAD))
+    stat = o["stat"].cpu().numpy().view(np.uint32)[:cnt]
+    stats["lines"] += int(ctr[2])
+    stats["spliced"] += int(ctr[2])
+    stats["handed_back"] += int(ctr[3])
+    stats["spliced_multi"] += int(ctr[4])
+    stats["spliced_refused"] += int(ctr[5])
+    stats["spliced_no_pair"] += int(ctr[6])
+    names = b["names"]
+    refused = [bytes(names[int(noff[j]):int(noff[j + 1])].cpu().numpy().tobytes())
+               for j in np.flatnonzero((stat != HSA_SL_OK) & (stat != HSA_SL_NONE) & (stat != HSA_SL_NOPAIR))]
+    return o, int(ctr[1]), stat, refused
+
+
+def _run_batch(gi, chr_names, b, opt, out, state, stats, splice=False):
     """Steps 2 to 5 for a merged batch; returns the generator's state and, per job, whether
     it got a line."""
     import torch
     n = b["n_jobs"]
     local, n_stacks, rg_b = chain.local_regime(opt, b["max_all"])      # bwtaln.c:254, :273-276
     assert local["max_diff"] == b["thr"]
+    if splice and n_stacks > HSA_SP_MAX_STACKS:
+        raise ValueError(f"the splice path with {n_stacks} score buckets (over {HSA_SP_MAX_STACKS}) is not built")
     opt["mode"] &= ~MODE_GAPE                               # :261, through aux->opt: it stays
     has_line = np.zeros(n, bool)
     if n == 0:
@@ -366,7 +448,19 @@ def _run_batch(gi, chr_names, b, opt, out, state, stats):
     if kept_sticky:
         opt["seed_len"] = SEED_NONE
     parts = _runs(b["has_qual"], 0, min(switch + 1, n))
-    parts = [(t1, f, c) for f, c in parts]
+    s1 = s2 = None
+    if splice:
+        # bwt_splice_match always gets &local_opt (bwtaln.c:363).  For the first read without a
+        # hit :331 wrote the read's own max_diff through aux->opt, which was still the caller's
+        # block: local_opt.max_diff is the batch's there.  From the next read on aux->opt is
+        # &local_opt and :331 writes each read's own into it.
+        srg = chain.splice_regimes(local, n_stacks)
+        if switch < n:
+            jobs1 = b["jobs"][:(switch + 1) * JOB_DTYPE.itemsize].clone()
+            jobs1.view(torch.int32).view(-1, 6)[switch, 3] = local["max_diff"]
+            s1 = chain.splice32(gi, b, t1, 0, switch + 1, srg, jobs=jobs1)
+            stats["spliced_sent"] += int(s1["sp_ctr"][0])
+    parts = [(t1, f, c, s1) for f, c in parts]
     stats["searched"] += n
     if switch < n - 1:
         first2 = switch + 1
@@ -385,17 +479,38 @@ def _run_batch(gi, chr_names, b, opt, out, state, stats):
                 jobs = [int(rec[r, 3]) for r in skip if rec[r, 0] == HSA_RD_SEARCHED]
                 if jobs:                                    # the reference did not search them: no hits
                     if t2 is t1:
-                        t2 = dict(t1, n_aln=t1["n_aln"].clone())
-                    t2["n_aln"][torch.tensor(jobs, device="cuda") - t2["first"]] = 0
+                        t2 = dict(t1, n_aln=t1["n_aln"].clone(), flags=t1["flags"].clone())
+                    at = torch.tensor(jobs, device="cuda") - t2["first"]
+                    t2["n_aln"][at] = 0
+                    t2["flags"][at] = 0                     # ... and did not send them to bwt_splice_match
                     stats["n_drop_after_switch"] += len(jobs)
-        parts += [(t2, f, c) for f, c in _runs(b["has_qual"], first2, n)]
-    for t, first, cnt in parts:
+        if splice:
+            s2 = chain.splice32(gi, b, t2, first2, n - first2, srg)
+            stats["spliced_sent"] += int(s2["sp_ctr"][0])
+        parts += [(t2, f, c, s2) for f, c in _runs(b["has_qual"], first2, n)]
+    if splice:
+        cb, coff = sam.pack_strings(chr_names)
+        up = lambda a: chain.to_device(a if len(a) else np.zeros(1, a.dtype))
+        chrs = dict(chrs=up(cb), chr_off=up(coff), n=len(chr_names),
+                    max_chr=int(np.diff(coff.astype(np.int64)).max()) if len(chr_names) else 0)
+    for t, first, cnt, s in parts:
+        if s is not None:
+            t = _splice_hits(t, s, first, cnt, stats)
         sub, state = chain.choose64(gi, b, t, first, cnt, state)
         m = chain.refine64(gi, sub)
         q = (b["quals"], b["qual_off"][first:]) if b["has_qual"][first] else None
-        text, _, stat, ctr = sam.device_sam(gi, m, (b["names"], b["name_off"][first:]), q, chr_names, max_top2=opt["max_top2"],
-                                            comp_read=bool(opt["mode"] & MODE_COMPREAD))
-        out.write(text)
+        text, off, stat, ctr = sam.device_sam(gi, m, (b["names"], b["name_off"][first:]), q, chr_names, max_top2=opt["max_top2"],
+                                              comp_read=bool(opt["mode"] & MODE_COMPREAD), on_device=s is not None)
+        if s is not None:
+            # the two writers' lines in read order (hsa_sam_merge_device), then one copy to the host
+            o2, written2, stat2, refused = _splice_lines(gi, b, s, first, cnt, chrs, bool(b["has_qual"][first]), opt, stats)
+            mo, mc = chain.sam_merge(gi, cnt, (text, int(ctr[1]), off), (o2["out"], written2, o2["line_off"]))
+            assert int(mc[0]) == int(mc[1]) == int(ctr[1]) + written2
+            out.write(mo["out"][:int(mc[1])].cpu().numpy().tobytes())
+            stats["refused_names"] += refused
+            stat = np.where(stat2 == 0, 0, stat)
+        else:
+            out.write(text)
         has_line[first:first + cnt] = stat == 0
         stats["lines"] += int(ctr[2])
         stats["refused"] += int(ctr[4]) + int(ctr[5]) + int(ctr[6])
@@ -412,11 +527,14 @@ def _read_input(data_or_path) -> bytes:
         return f.read()
 
 
-def align_fastq(gi, chr_names, data_or_path, opts, out, batch_reads=BATCH_READS, rng_state=HSA_DRAND48_SEED0, unaligned=None):
+def align_fastq(gi, chr_names, data_or_path, opts, out, batch_reads=BATCH_READS, rng_state=HSA_DRAND48_SEED0, unaligned=None,
+                splice=False):
     """FASTQ (bytes, or a path; gzip is read through Python's gzip) to SAM text written to
     `out` (a binary file object), as the module docstring states it.  opts: an option dict
     (default_opts / parse_options), not modified.  unaligned: a binary file object for the
-    reads without a line.  Returns (the drand48 state after the last read, statistics)."""
+    reads without a line.  splice: send the reads without a main-search hit through the splice
+    path and print its lines too (the module docstring's contract).  Returns (the drand48 state
+    after the last read, statistics)."""
     import collections
     import torch
     data = _read_input(data_or_path)
@@ -425,9 +543,18 @@ def align_fastq(gi, chr_names, data_or_path, opts, out, batch_reads=BATCH_READS,
         raise ValueError("quality trimming, barcodes, the Casava filter, Illumina-1.3 qualities and BAM input are not built")
     if not opt["mode"] & MODE_COMPREAD:
         raise ValueError("colour-space reads (-c) are not built")
+    if splice:
+        if gi.is64():
+            raise ValueError("the splice path for a text of 2^32 characters or more is not built")
+        if opt["fnr"] <= 0 and chain.local_regime(opt, 0)[1] > HSA_SP_MAX_STACKS:
+            raise ValueError(f"the splice path with more than {HSA_SP_MAX_STACKS} score buckets is not built")
     d_table = torch.from_numpy(_table(opt["fnr"])).cuda() if opt["fnr"] > 0 else None
     stats = collections.Counter(reads=0, searched=0, searched_again=0, n_drop=0, polyat=0, n_drop_after_switch=0, lines=0,
                                 refused=0, batches=0, device_records=0, host_records=0)
+    if splice:
+        stats.update(spliced_sent=0, spliced=0, spliced_unspliced=0, spliced_no_pair=0, handed_back=0, spliced_multi=0,
+                     spliced_refused=0)
+        stats["refused_names"] = []
     pos, state, window = 0, int(rng_state), max(4 << 20, 1024 * int(batch_reads))
     while pos < len(data):
         start = pos
@@ -442,7 +569,7 @@ def align_fastq(gi, chr_names, data_or_path, opts, out, batch_reads=BATCH_READS,
         stats["polyat"] += int((rec[:, 0] == HSA_RD_POLYAT).sum())
         stats["device_records"] += sum(s["t"]["n_loaded"] for s in segs if s["kind"] == "dev")
         stats["host_records"] += sum(len(s["p"]["names"]) for s in segs if s["kind"] == "host")
-        state, has_line = _run_batch(gi, chr_names, b, opt, out, state, stats)
+        state, has_line = _run_batch(gi, chr_names, b, opt, out, state, stats, splice=splice)
         if unaligned is not None:
             p = reads.parse_host(data[start:pos], len(rec))
             assert len(p["names"]) == len(rec)
@@ -471,7 +598,7 @@ def main(argv=None) -> int:
         print(f"hsa_amd.align: {e}", file=sys.stderr)
         return 1
     if len(rest) < 2:
-        print("usage: python -m hsa_amd.align [bwa-aln options] [--header] [--unaligned FILE] [-f OUT] <prefix> <in.fq>",
+        print("usage: python -m hsa_amd.align [bwa-aln options] [--header] [--unaligned FILE] [--splice] [-f OUT] <prefix> <in.fq>",
               file=sys.stderr)
         return 1
     gi, chrs = open_index64(rest[0])
@@ -480,7 +607,7 @@ def main(argv=None) -> int:
     try:
         if extra["header"]:
             out.write(sam_header(rest[0]))
-        _, stats = align_fastq(gi, chrs, rest[1], opts, out, unaligned=un)
+        _, stats = align_fastq(gi, chrs, rest[1], opts, out, unaligned=un, splice=extra.get("splice", False))
         out.flush()
     finally:
         if un:
@@ -488,7 +615,7 @@ def main(argv=None) -> int:
         if extra["out"]:
             out.close()
         gi.close()
-    print("[hsa_amd.align] " + ", ".join(f"{k} {v}" for k, v in stats.items()), file=sys.stderr)
+    print("[hsa_amd.align] " + ", ".join(f"{k} {v}" for k, v in stats.items() if k != "refused_names"), file=sys.stderr)
     return 0
 
 

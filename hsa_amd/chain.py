@@ -1,6 +1,8 @@
 """The device chain of the 64-bit path, stage by stage: search (hsa_search_device64), hit
 positions (hsa_hit_positions_device64), choose (hsa_choose_hits_device64), refine
-(hsa_refine_rows_device64) and the SAM lines (hsa_sam_lines_device64).
+(hsa_refine_rows_device64) and the SAM lines (hsa_sam_lines_device64); beside them, for the
+reads the search leaves without a hit, the splice search (hsa_splice_device) and the spliced
+reads' lines (hsa_splice_lines_device).
 
 The convention.  Everything a stage reads or writes is a device tensor (anything with
 data_ptr()) in one dict, by these keys; a stage returns the dict it was given with its own
@@ -13,7 +15,10 @@ outputs added, so the dict of the last stage holds the whole chain:
   positions       pos_off, pos, pos_hit, pos_ctr (optional for the SAM lines), pos_cap:
                   written by hit_positions64 or, the chosen and XA rows, by choose64;
   choose          sel, sel64, rng (the generator's state after the last read);
-  refine          rows, rpos, cigar, md, ctr, cigar_stride, md_stride.
+  refine          rows, rpos, cigar, md, ctr, cigar_stride, md_stride;
+  splice          res (HSA_SP_RES_WORDS words per job), sp_ctr, sp_first (the batch's job
+                  the arrays start at), sp_flags and sp_n_aln (what the call was given);
+  splice lines    line_off, stat, ctr, out, rows (SL_ROW_WORDS words per job), cigar.
 
 Every stage is a builder and a driver.  The builder (`*_batch`) allocates the outputs and
 returns the filled ctypes struct of _lib with the tensors; a probe builds once and times many
@@ -24,8 +29,9 @@ from __future__ import annotations
 import numpy as np
 
 from . import reads
-from ._lib import (ALN64_WORDS, HSA_RF_MAX_LEN, HSA_RF_MD, JOB_DTYPE, RF_ROW_WORDS, ChooseBatch64, DeviceBatch, HitPosBatch64,
-                   HsaError, RefineBatch64, SamBatch64, regime_of)
+from ._lib import (ALN64_WORDS, HSA_RF_MAX_LEN, HSA_RF_MD, JOB_DTYPE, RF_ROW_WORDS, SL_ROW_WORDS, SP_RES_WORDS, ChooseBatch64,
+                   DeviceBatch, HitPosBatch64, HsaError, RefineBatch64, SamBatch64, SamMergeBatch, SpliceBatch, SpliceLinesBatch,
+                   anchor_regime, ext_regime, regime_of)
 
 N_MULTI = 3                      # bwtaln.c:514
 
@@ -185,6 +191,96 @@ def refine64(gi, sub, cigar_stride=16, md_stride=128):
         if int(o["ctr"][1 + HSA_RF_MD]) == 0 or md_stride >= 16384:
             return o
         cigar_stride, md_stride = cigar_stride * 2, md_stride * 2
+
+
+# ---------------------------------------------------------------- the splice search and its lines
+def splice_regimes(local, n_stacks):
+    """(seed, anchor, extension) regimes of bwt_splice_match for a batch's local options:
+    aux_seed (bwtgap.c:769-774) and aux_ext (:776-782)."""
+    from . import splice
+    so = splice.seed_options(local)
+    return (regime_of(so, n_stacks, so["max_diff"]), anchor_regime(local, n_stacks, local["max_diff"]),
+            ext_regime(local, n_stacks, local["max_diff"]))
+
+
+def splice32_batch(b, t, first, n, jobs=None, flags=None):
+    """(SpliceBatch, the splice tensors res, sp_ctr, sp_first) for jobs [first, first + n) of
+    the batch b, whose search tensors are t.  jobs, flags: tensors to take these jobs' rows
+    and flags from instead of the batch's and the search's (from job `first` on)."""
+    k = first - t["first"]
+    jobs = b["jobs"][first * JOB_DTYPE.itemsize:] if jobs is None else jobs
+    flags = t["flags"][k:] if flags is None else flags
+    o = dict(res=_new(max(n, 1) * SP_RES_WORDS, "int32"), sp_ctr=_new(8, "int64"), sp_first=first, sp_flags=flags,
+             sp_n_aln=t["n_aln"][k:])
+    sb = SpliceBatch(d_jobs=jobs.data_ptr(), n_jobs=n, d_codes=b["codes"].data_ptr(), d_flags=flags.data_ptr(),
+                     d_n_aln=o["sp_n_aln"].data_ptr(), d_res=o["res"].data_ptr(), d_counters=o["sp_ctr"].data_ptr(),
+                     max_len=b["max_len"])
+    return sb, o
+
+
+def splice32(gi, b, t, first, n, regimes, jobs=None, flags=None):
+    """hsa_splice_device over jobs [first, first + n) of the batch: bwt_splice_match of every
+    job the search flagged HSA_F_FALLBACK and left without a hit, under the (seed, anchor,
+    extension) regimes of splice_regimes.  Each read's max_diff is its job's.  Returns the
+    splice tensors: res (HSA_SP_RES_WORDS words per job, written for those reads only)."""
+    sb, o = splice32_batch(b, t, first, n, jobs, flags)
+    _call(gi.splice_device, regimes[0], regimes[1], regimes[2], sb)
+    return o
+
+
+def splice_lines_batch(b, s, first, n, strings, n_chr, max_line, out_cap, cigar_stride=33, flag=0, max_top2=30, comp_read=True):
+    """(SpliceLinesBatch, the output tensors line_off, stat, ctr, out, rows, cigar) for jobs
+    [first, first + n) of the batch b and the splice tensors s (of splice32).  strings: as
+    sam_lines64_batch takes them, the offsets from job `first` on."""
+    import torch
+    k = first - s["sp_first"]
+    o = dict(line_off=_new(n + 1, "int64"), stat=_new(max(n, 1), "int32"), ctr=_new(8, "int64"),
+             out=torch.empty(max(out_cap, 1), dtype=torch.uint8, device="cuda"), rows=_new(max(n, 1) * SL_ROW_WORDS, "int32"),
+             cigar=_new(max(n, 1) * cigar_stride, "int32"), cigar_stride=cigar_stride)
+    lb = SpliceLinesBatch(d_jobs=b["jobs"].data_ptr() + first * JOB_DTYPE.itemsize, n_jobs=n, d_codes=b["codes"].data_ptr(),
+                          d_flags=s["sp_flags"][k:].data_ptr(), d_n_aln=s["sp_n_aln"][k:].data_ptr(),
+                          d_res=s["res"][k * SP_RES_WORDS:].data_ptr(), d_names=strings["names"].data_ptr(),
+                          d_name_off=strings["name_off"].data_ptr(), d_quals=_ptr(strings, "quals"),
+                          d_qual_off=_ptr(strings, "qual_off"), d_chr_names=strings["chrs"].data_ptr(),
+                          d_chr_off=strings["chr_off"].data_ptr(), n_chr=n_chr, flag=int(flag), max_top2=int(max_top2),
+                          comp_read=int(bool(comp_read)), max_len=b["max_len"], max_line=max_line, cigar_stride=cigar_stride,
+                          d_rows=o["rows"].data_ptr(), d_cigar=o["cigar"].data_ptr(), d_line_off=o["line_off"].data_ptr(),
+                          d_out=o["out"].data_ptr(), out_cap=out_cap, d_line_stat=o["stat"].data_ptr(),
+                          d_counters=o["ctr"].data_ptr())
+    return lb, o
+
+
+def splice_lines(gi, b, s, first, n, strings, n_chr, max_line, out_cap, **kw):
+    """hsa_splice_lines_device over jobs [first, first + n) with room for out_cap bytes, run a
+    second time with counters[0] bytes of room when the first reports wanted > written: (the
+    output tensors, the counters as 8 u64 on the host)."""
+    for _ in range(2):
+        lb, o = splice_lines_batch(b, s, first, n, strings, n_chr, max_line, out_cap, **kw)
+        _call(gi.splice_lines, lb)
+        ctr = o["ctr"].cpu().numpy().view(np.uint64)
+        if int(ctr[0]) <= int(ctr[1]):
+            break
+        out_cap = int(ctr[0])
+    return o, ctr
+
+
+def sam_merge_batch(n, a, b):
+    """(SamMergeBatch, the output tensors line_off, out, ctr) for the lines of two writers over
+    the same n reads.  a, b: (the text tensor, its bytes, the writer's line_off tensor)."""
+    import torch
+    cap = int(a[1]) + int(b[1])
+    o = dict(line_off=_new(n + 1, "int64"), out=torch.empty(max(cap, 1), dtype=torch.uint8, device="cuda"), ctr=_new(8, "int64"))
+    mb = SamMergeBatch(n_jobs=n, d_line_off_a=a[2].data_ptr(), d_text_a=a[0].data_ptr(), text_a_len=int(a[1]),
+                       d_line_off_b=b[2].data_ptr(), d_text_b=b[0].data_ptr(), text_b_len=int(b[1]),
+                       d_line_off=o["line_off"].data_ptr(), d_out=o["out"].data_ptr(), out_cap=cap, d_counters=o["ctr"].data_ptr())
+    return mb, o
+
+
+def sam_merge(gi, n, a, b):
+    """hsa_sam_merge_device: (the output tensors, the counters as 8 u64 on the host)."""
+    mb, o = sam_merge_batch(n, a, b)
+    _call(gi.sam_merge, mb)
+    return o, o["ctr"].cpu().numpy().view(np.uint64)
 
 
 # ---------------------------------------------------------------- SAM lines

@@ -129,10 +129,10 @@ extern "C" int hsa_index_release_scratch(hsa_index_t *ix)
     HSA_HIP(hipStreamSynchronize(ix->stream));
     hsa_scratch_free(ix->main); hsa_scratch_free(ix->big); hsa_scratch_free(ix->huge);
     void **bufs[] = {&ix->d_pf, &ix->d_pf2, &ix->d_sp, &ix->d_any, &ix->d_any_aux, &ix->d_help, &ix->d_hp, &ix->d_rf,
-                     &ix->d_ch, &ix->d_sm, &ix->d_rd};
+                     &ix->d_ch, &ix->d_sm, &ix->d_rd, &ix->d_sl};
     size_t *caps[] = {&ix->d_pf_cap, &ix->d_pf2_cap, &ix->d_sp_cap, &ix->d_any_cap, &ix->d_any_aux_cap, &ix->d_help_cap,
-                      &ix->d_hp_cap, &ix->d_rf_cap, &ix->d_ch_cap, &ix->d_sm_cap, &ix->d_rd_cap};
-    for (int i = 0; i < 11; ++i) {
+                      &ix->d_hp_cap, &ix->d_rf_cap, &ix->d_ch_cap, &ix->d_sm_cap, &ix->d_rd_cap, &ix->d_sl_cap};
+    for (int i = 0; i < 12; ++i) {
         if (*bufs[i]) (void)hipFree(*bufs[i]);
         *bufs[i] = nullptr;
         *caps[i] = 0;
@@ -648,6 +648,7 @@ extern "C" void hsa_index_free(hsa_index_t *ix)
     (void)hipFree(ix->d_sa64); (void)hipFree(ix->d_blocks64); (void)hipFree(ix->d_hp);
     (void)hipFree(ix->d_text64); (void)hipFree(ix->d_rf); (void)hipFree(ix->d_ch);
     (void)hipFree(ix->d_sm);
+    (void)hipFree(ix->d_sl);
     (void)hipFree(ix->d_rd);
     if (ix->d_sp) (void)hipFree(ix->d_sp);
     (void)hipFree(ix->d_trie_w);

@@ -124,6 +124,8 @@ struct hsa_index {
     // hsa_reads_device: newline counts per tile, line starts, per-record fields, the scans
     void *d_rd = nullptr; size_t d_rd_cap = 0;
     StageTimer rd_t{HSA_RD_LAUNCHES};              // around its launches (hsa_reads_timing)
+    // hsa_splice_lines_device: the segments' refine inputs and outputs, line lengths, the scan
+    void *d_sl = nullptr; size_t d_sl_cap = 0;
     // the splice path's kernel (hsa_splice.hip): per-lane state, stacks, buffers
     void *d_sp = nullptr; size_t d_sp_cap = 0;
     uint64_t *d_ctr = nullptr;
@@ -201,6 +203,9 @@ struct PfDev {
 // per read); ext_rg: the extension regime (local_opt with max_gape 3, bwtgap.c:777-782)
 int hsa_splice_device_launch(hsa_index *ix, const PfDev &pd, const hsa_regime_t &ext_rg, uint32_t *d_res,
                              unsigned long long *d_ctr, hipStream_t st);
+// hsa_refine_rows_device64's launches for a checked batch (hsa_refine.hip); all_dp: rows
+// without a gap are aligned too, as the reference aligns the segments of a spliced read
+int hsa_refine_rows_launch(hsa_index *ix, const hsa_refine_batch64_t *b, hipStream_t st, bool all_dp, const char *what);
 int hsa_scratch_reserve(SearchScratch &s, size_t lanes, size_t pcap, size_t hcap, size_t link_bytes = 2);
 void hsa_scratch_free(SearchScratch &s);
 // HSA_E_ARG unless the index fits the 32-bit entry points (bwtint_t, 2BWT-Interface.h:26)

@@ -84,6 +84,7 @@ struct RefineArgs {
     uint8_t *wave;                 // per-wave scratch: tb_rows x tb_stride bytes, then the runs
     size_t wave_bytes, tb_bytes;
     uint32_t tb_stride, ring, win_cap;
+    uint32_t all_dp;               // every row is aligned, a row without a gap too (the spliced segments)
 };
 
 struct RfRow {
@@ -190,7 +191,7 @@ __global__ void __launch_bounds__(256) k_refine_rows(RefineArgs a)
         rf_row(a, t, r);
         if (r.pos == ~0ull || r.ori == ~0ull) st = HSA_RF_POS;
         else if (r.len == 0 || r.len > a.max_len || r.gap > HSA_RF_MAX_GAP) st = HSA_RF_CAP;
-        else if (r.gap == 0) st = r.pos + r.len > a.text.n ? HSA_RF_TEXT : rf_ungapped(a, t, r);
+        else if (r.gap == 0 && !a.all_dp) st = r.pos + r.len > a.text.n ? HSA_RF_TEXT : rf_ungapped(a, t, r);
         else st = r.pos >= a.text.n ? HSA_RF_TEXT : RF_DP;
         if (st != RF_DP && st != HSA_RF_OK && st != HSA_RF_MD) rf_write_row(a, t, st, 0u, 0u, 0u, 0u, 0u, r.pos, r.ori);
     }
@@ -457,7 +458,13 @@ extern "C" int hsa_refine_rows_device64(hsa_index_t *ix, const hsa_refine_batch6
     if (!ix->wide) { hsa_set_error("%s: not a 64-bit index (hsa_index_create_device64)", what); return HSA_E_ARG; }
     if (!b || b->n_jobs < 0 || !b->d_counters || b->max_len < 0) { hsa_set_error("%s: bad arguments", what); return HSA_E_ARG; }
     HSA_HIP(hipSetDevice(ix->device));
-    hipStream_t st = hsa_stage_stream(stream, ix->stream);
+    return hsa_refine_rows_launch(ix, b, hsa_stage_stream(stream, ix->stream), false, what);
+}
+
+// The call's launches on `st`; all_dp: the splicing branch of bwa_refine_gapped
+// (bwtse.c:567-574), where every row is aligned whatever its gap count (hsa_splice_rows.hip).
+int hsa_refine_rows_launch(hsa_index *ix, const hsa_refine_batch64_t *b, hipStream_t st, bool all_dp, const char *what)
+{
     HSA_HIP(hipMemsetAsync(b->d_counters, 0, 8 * sizeof(uint64_t), st));
     if (b->n_jobs == 0 || b->pos_cap == 0) return 0;           // no rows
     if (!b->d_jobs || !b->d_codes || !b->d_hit_off || !b->d_hits || !b->d_pos_off || !b->d_pos || !b->d_pos_hit ||
@@ -510,6 +517,7 @@ extern "C" int hsa_refine_rows_device64(hsa_index_t *ix, const hsa_refine_batch6
     A.ctr = (unsigned long long *)b->d_counters;
     A.wave_bytes = wave_bytes; A.tb_bytes = tb_bytes;
     A.tb_stride = tb_stride; A.ring = ring; A.win_cap = win_cap;
+    A.all_dp = all_dp ? 1u : 0u;
     hipLaunchKernelGGL(k_refine_rows, dim3((unsigned)((b->pos_cap + 255u) / 256u)), dim3(256), 0, st, A);
     HSA_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_refine_dp, dim3((unsigned)waves), dim3(64), lds, st, A);

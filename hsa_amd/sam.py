@@ -12,8 +12,11 @@ Two ways to the same bytes:
   qualities, chromosome names, laid out by pack_strings), sizes the output, runs the call
   and returns the text after one copy to the host.
 
+spliced_line is the same restatement for a spliced read (type BWA_TYPE_SPLICING, XT:A:S):
+the text hsa_splice_lines_device (hsa_amd/csrc/hsa_splice_rows.hip) is tested against.
+
 Not printed: RG / BC / XC tags (no read group, barcode or trimmed read reaches the 64-bit
-path) and spliced reads."""
+path) and the XA list of a spliced read with more than one pair."""
 from __future__ import annotations
 
 import numpy as np
@@ -80,6 +83,37 @@ def sam_line(name, seq_codes, qual, chr_names, sel, sel64, rows, rpos, cigar, md
     return "\t".join(out)
 
 
+CIGAR_OPS = "MIDNSHP=X"      # bwtse.c:713
+
+
+def spliced_line(name, seq_codes, qual, chr_name, ori_pos, cigar, strand, c1, c2, n_mm, max_top2=30, flag=0,
+                 comp_read=True) -> str:
+    """The line of a spliced read (bwa_print_sam1 for type BWA_TYPE_SPLICING, bwtse.c:677-799),
+    without the newline.
+
+    chr_name, ori_pos: segment 0's chromosome and 1-based position; cigar: the merged CIGAR
+    as (op, length) pairs, op an index into "MIDNSHP=X" (hsa_amd.splice.merge_cigar); strand:
+    res_aln[0]'s; c1, c2: the capped row count bwt_aln2pos_splicing leaves in both
+    (bwtse.c:310-315); n_mm: mm of segment 0 plus mm of segment 1 (:594).  mapQ is 0 (the
+    value of :345 is dropped), NM is 0 (nm is never computed for these reads), XO and XG are
+    0 (gap is never set), and there is no MD."""
+    seq_codes = np.asarray(seq_codes, np.uint8)
+    if strand:
+        flag |= SAM_FSR
+    out = [name, str(flag), chr_name, str(int(ori_pos)), "0", "".join(f"{int(l)}{CIGAR_OPS[int(op)]}" for op, l in cigar),
+           "*", "0", "0"]
+    if strand == 0:
+        out.append("".join(SEQ_FWD[c] for c in seq_codes))
+    else:
+        out.append("".join(SEQ_REV[c] for c in seq_codes[::-1]))
+    out.append("*" if qual is None else (qual[::-1] if strand else qual))
+    out += [f"XT:A:{XT[4]}", f"{'NM' if comp_read else 'CM'}:i:0", f"X0:i:{int(c1)}"]
+    if c1 <= max_top2:
+        out.append(f"X1:i:{int(c2)}")
+    out += [f"XM:i:{int(n_mm)}", "XO:i:0", "XG:i:0"]
+    return "\t".join(out)
+
+
 # ---------------------------------------------------------------- the batch path
 def pack_strings(items):
     """Strings (str or bytes) laid out for the device: (their bytes end to end as a uint8
@@ -104,7 +138,7 @@ def line_bound(max_name, max_len, max_chr, cigar_stride, md_stride, max_xa) -> i
     return min(n, HSA_SAM_MAX_LINE)
 
 
-def device_sam(gi, dev, names, quals, chr_names, max_top2=30, flag=0, comp_read=True):
+def device_sam(gi, dev, names, quals, chr_names, max_top2=30, flag=0, comp_read=True, on_device=False):
     """The SAM text of a batch: (text as bytes, line_off (n + 1 u64), line_stat (n u32),
     counters (8 u64)) of one hsa_sam_lines_device64 call, run a second time with
     counters[0] bytes of room when the first reports wanted > written.
@@ -114,7 +148,8 @@ def device_sam(gi, dev, names, quals, chr_names, max_top2=30, flag=0, comp_read=
     (FASTQ comment cut); quals: their quality strings, or None ("*"); chr_names: by chrID.
     Names and qualities that are on the device already (hsa_amd.reads.load_device) are given
     as a pair of tensors instead of a list: (the bytes, the n + 1 u64 offsets of these reads; a
-    sub-range's offsets are a view from its first read on)."""
+    sub-range's offsets are a view from its first read on).  on_device: the text and line_off stay
+    device tensors (the text's first counters[1] bytes hold)."""
     import torch
     from . import chain
     from ._lib import JOB_DTYPE
@@ -151,6 +186,8 @@ def device_sam(gi, dev, names, quals, chr_names, max_top2=30, flag=0, comp_read=
     o, ctr = chain.sam_lines64(gi, dev, t, len(chr_names), max_line, cap, flag=flag, max_top2=max_top2, comp_read=comp_read)
     out = o["out"]
     written = int(ctr[1])
+    if on_device:
+        return out, o["line_off"], o["stat"].cpu().numpy().view(np.uint32)[:n], ctr
     host = torch.empty(max(written, 1), dtype=torch.uint8).pin_memory()
     host[:written].copy_(out[:written])
     torch.cuda.synchronize()

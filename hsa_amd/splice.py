@@ -172,6 +172,68 @@ def seed_jobs(batch):
     return jobs, mg
 
 
+# ---------------------------------------------------------------- after the search: pairing the two segments
+# The restatements hsa_splice_lines_device (hsa_amd/csrc/hsa_splice_rows.hip) is tested against.
+ROW_COLS = ("aln_id", "seq_id", "ori_pos", "occ_pos")
+SPLICE_MIN, SPLICE_MAX = 50, 50000          # bwtse.c:219
+U32 = 0xFFFFFFFF
+
+
+def segment_rows(k: int, l: int) -> int:
+    """The SA rows bwt_aln2pos_splicing looks up for a segment (bwtse.c:320): k, k + 1, ...
+    while <= l and < k + 50."""
+    return max(0, min(l, k + 49) - k + 1)
+
+
+def capped_multi(k0: int, l0: int, k1: int, l1: int) -> int:
+    """n_multi of bwtse.c:310-312, the value of c1 and c2 (X0, X1)."""
+    return min(100, (l0 - k0 + l1 - k1 + 2) & U32)
+
+
+def pair_segments(rows):
+    """bwt_combine_segment_splice (bwtse.c:197-235) over the rows of both segments in the
+    order bwt_aln2pos_splicing fills them (segment 0's, then segment 1's): rows is an (n, 4)
+    integer array of ROW_COLS.  Returns (n_res, index): index[2 p], index[2 p + 1] are the
+    rows (indices into `rows`) of pair p as the reference leaves them at multi[2 p],
+    multi[2 p + 1].
+
+    Two rows are one pair as they stand, unsorted and whatever lies between them (:204).
+    Otherwise the rows are sorted by occ_pos -- they are distinct SA rows, so their positions
+    are distinct and any correct sort gives the reference's order -- and one pass keeps the
+    pairs (segment 0 directly followed by segment 1 on one chromosome, 50 <= d <= 50 000) at
+    the shortest distance so far.  The reference moves a kept pair to multi[2 (n_res - 1)]
+    in place; the k-th kept pair starts at a sorted index >= 2 (k - 1), so a move never
+    touches a row the loop has yet to read, and `if (i == 0) continue` skips a move of rows
+    0, 1 onto themselves: collecting the pairs in a list is the same."""
+    rows = np.asarray(rows, np.int64).reshape(-1, 4)
+    n = len(rows)
+    if n == 2:
+        return 1, [0, 1]
+    order = sorted(range(n), key=lambda r: (int(rows[r, 3]), r))
+    shortest, pairs = U32, []
+    for i in range(n - 1):
+        a, b = rows[order[i]], rows[order[i + 1]]
+        if a[0] != 0:
+            continue
+        d = int(b[3] - a[3]) & U32
+        if a[0] == b[0] or a[1] != b[1] or d > shortest:
+            continue
+        if d < SPLICE_MIN or d > SPLICE_MAX:
+            continue
+        if d < shortest:
+            shortest, pairs = d, [i]
+        else:
+            pairs.append(i)
+    return len(pairs), [order[i + s] for i in pairs for s in (0, 1)]
+
+
+def merge_cigar(cigar0, ori0: int, end0: int, cigar1, ori1: int):
+    """The merged CIGAR of a spliced read (bwtse.c:578-582): segment 0's ops, N of length
+    ori_pos1 - ori_pos0 - end0 (end0: segment 0's `end` field, all three after
+    refine_gapped_core's adjustments), segment 1's ops; (op, length) pairs, N = 3."""
+    return list(cigar0) + [(3, ori1 - ori0 - end0)] + list(cigar1)
+
+
 def run_seed_calls(gi, batch, n_stacks: int):
     """All seed calls of `batch` in one hsa_match_gap_batch pass.
     Returns (n_aln, hit_off, hits, widths after, stats)."""

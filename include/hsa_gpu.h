@@ -625,9 +625,10 @@ int hsa_index_set_text64_device(hsa_index_t *ix, uint32_t *d_text_lsb, uint64_t 
  * hsa_choose_hits_device64's (below: the chosen row and the XA rows, same layout).
  *
  * Not built, and left to the caller: bwa_correct_trimmed (:496-534, needs full_len, which
- * the device batch does not carry), spliced reads (N ops, :562-619), a 32-bit-record
- * (bwt_aln1_t) variant, and an on-disk format for 64-bit samples.  The drop-in's SAM stage
- * keeps the host's bwa_refine_gapped. */
+ * the device batch does not carry), a 32-bit-record (bwt_aln1_t) variant, and an on-disk
+ * format for 64-bit samples.  The segments of a spliced read (:562-619) are aligned by these
+ * kernels from hsa_splice_lines_device (below).  The drop-in's SAM stage keeps the host's
+ * bwa_refine_gapped. */
 typedef struct {
     const hsa_job_t *d_jobs; int n_jobs;
     const uint8_t *d_codes;
@@ -782,7 +783,8 @@ int hsa_choose_launch_times(hsa_index_t *ix, float *ms);
  * synchronise; scratch grows on the handle (hsa_index_release_scratch).  Null pointers and
  * inconsistent sizes: HSA_E_ARG.
  *
- * Not built: spliced reads (N ops, XT:A:S), trimmed reads (bwa_correct_trimmed, the XC
+ * Spliced reads (N ops, XT:A:S) have a writer of their own, hsa_splice_lines_device below.
+ * Not built: trimmed reads (bwa_correct_trimmed, the XC
  * tag, the reference's reversal of only `len` quality bytes of a full_len read), RG and BC
  * tags, paired reads, the @SQ header lines, a 32-bit-record (bwt_aln1_t) variant.  The
  * drop-in's host SAM stage stays as it is. */
@@ -823,6 +825,98 @@ int hsa_sam_lines_device64(hsa_index_t *ix, const hsa_sam_batch64_t *b, void *st
 #define HSA_SAM_LAUNCHES 3
 void hsa_sam_timing(int on);
 int hsa_sam_launch_times(hsa_index_t *ix, float *ms);
+
+/* ---- the SAM lines of spliced reads ----
+ * What the reference does with a read whose bwt_splice_match result is two records of type
+ * BWA_TYPE_SPLICING, after the search: bwt_aln2pos_splicing with bwt_combine_segment_splice
+ * (bwtse.c:295-348, :197-235), the splicing branch of bwa_refine_gapped (:562-595, over
+ * refine_gapped_core :380-440) and the XT:A:S line of bwa_print_sam1 (:677-799).  Python
+ * restatements: hsa_amd.splice.pair_segments / merge_cigar, hsa_amd.sam.spliced_line.
+ *
+ * Inputs: the batch (d_jobs, d_codes, names and qualities as hsa_sam_batch64_t takes them),
+ * d_flags and d_n_aln as hsa_splice_device took them (they say which jobs' d_res words were
+ * written), d_res of hsa_splice_device, the chromosome names.  Needs hsa_index_set_sa and a
+ * text (hsa_index_set_text), and an index under 2^32 characters (HSA_E_ARG otherwise).
+ *
+ * Outputs, in hsa_sam_lines_device64's conventions: d_line_off (n_jobs + 1 exclusive
+ * offsets, a read without a line has length 0), d_out / out_cap (nothing is written at or
+ * past out_cap), d_line_stat per read, d_counters: [0] bytes wanted, [1] bytes written,
+ * [2] lines, [3] reads the splice kernel handed back, [4] reads with more than one pair,
+ * [5] reads refused otherwise, [6] reads without a pair (the reference prints no line for
+ * them either), [7] spliced results seen.  d_rows: HSA_SL_ROW_WORDS u32 per read, written
+ * for every read: status, n_rows, n_splice, c1 (= c2: the capped row count of :310-312),
+ * strand, the merged n_cigar, then per segment chrID, 1-based position, text position,
+ * start, end and mm (after refine_gapped_core's adjustments when the status is
+ * HSA_SL_OK, as paired otherwise), the N length, mm0 + mm1, and the two segments' n_cigar.
+ * d_cigar: the merged CIGAR, cigar_stride words per read ((op << 28) | length, op an index
+ * into "MIDNSHP=X").
+ *
+ * A read gets the reference's line or none (d_line_stat): HSA_SL_NONE not a spliced
+ * result (not sent to the splice path, or n_aln is not 2 records of type 4); HSA_SL_HANDED
+ * hsa_splice_device's status is > 0; HSA_SL_NOPAIR no pair of rows combines (the reference
+ * sets BWA_TYPE_NO_MATCH, :339-342); HSA_SL_MULTI more than one pair (the reference prints
+ * the others as XA in a format of its own, :596-618: not built); HSA_SL_REFINE a segment's
+ * alignment was not answered; HSA_SL_POS a paired row lies in no chromosome block, or the
+ * two on different chromosomes; HSA_SL_INTRON the N length is not positive; HSA_SL_INPUT a
+ * record field, string offset or CIGAR outside what the layout holds, or a line past
+ * max_line.
+ *
+ * Four launches and a scan on the caller's stream (NULL: the index's own), no
+ * synchronisation, no atomic places a byte: one wavefront per read pairs the rows (lanes
+ * along the SA walks and the sort), the two segments go through hsa_refine_rows_device64's
+ * kernels with every row aligned, one lane per read merges and measures, rocPRIM scans,
+ * one wavefront per read writes.  Scratch grows on the handle (hsa_index_release_scratch). */
+#define HSA_SL_ROW_WORDS 24
+#define HSA_SL_OK     0u
+#define HSA_SL_NONE   1u
+#define HSA_SL_HANDED 2u
+#define HSA_SL_NOPAIR 3u
+#define HSA_SL_MULTI  4u
+#define HSA_SL_REFINE 5u
+#define HSA_SL_POS    6u
+#define HSA_SL_INTRON 7u
+#define HSA_SL_INPUT  8u
+typedef struct {
+    const hsa_job_t *d_jobs; int n_jobs;
+    const uint8_t *d_codes;
+    const uint32_t *d_flags; const int32_t *d_n_aln;         /* as hsa_splice_batch_t */
+    const uint32_t *d_res;                                   /* HSA_SP_RES_WORDS per job */
+    const uint8_t *d_names; const uint64_t *d_name_off;      /* n_jobs + 1 */
+    const uint8_t *d_quals; const uint64_t *d_qual_off;      /* n_jobs + 1, or both NULL */
+    const uint8_t *d_chr_names; const uint64_t *d_chr_off;   /* n_chr + 1 */
+    uint32_t n_chr;
+    uint32_t flag;                   /* the reads' extra_flag */
+    int32_t max_top2;                /* gap_opt_t.max_top2 */
+    int32_t comp_read;               /* BWA_MODE_COMPREAD: NM, else CM */
+    int32_t max_len;                 /* longest read of the batch */
+    uint32_t max_line;               /* the longest line the batch can have, '\n' included */
+    uint32_t cigar_stride;           /* ops of a merged CIGAR */
+    uint32_t pad;
+    uint32_t *d_rows;                /* HSA_SL_ROW_WORDS u32 per job */
+    uint32_t *d_cigar;               /* cigar_stride u32 per job */
+    uint64_t *d_line_off;            /* n_jobs + 1 */
+    uint8_t *d_out; uint64_t out_cap;
+    uint32_t *d_line_stat;           /* n_jobs */
+    uint64_t *d_counters;            /* >= 8 u64 */
+} hsa_splice_lines_batch_t;
+int hsa_splice_lines_device(hsa_index_t *ix, const hsa_splice_lines_batch_t *b, void *stream);
+/* The lines of two writers over the same reads (hsa_sam_lines_device64's and
+ * hsa_splice_lines_device's: a read has a line from at most one of them) as one text in read
+ * order: d_line_off[j] is the sum of the two inputs' offsets, and read j's bytes are writer
+ * a's, then writer b's.  A scan over the summed lengths and one copy kernel (a wavefront per
+ * read, 16-byte stores where source and destination are congruent modulo 16), on the caller's
+ * stream, no synchronisation.  text_a_len / text_b_len: the bytes the two texts hold (a line
+ * whose offsets run backwards or past them counts as empty).  d_counters (>= 8 u64): [0]
+ * bytes wanted, [1] bytes written; nothing is written at or past out_cap. */
+typedef struct {
+    int n_jobs;
+    const uint64_t *d_line_off_a; const uint8_t *d_text_a; uint64_t text_a_len;
+    const uint64_t *d_line_off_b; const uint8_t *d_text_b; uint64_t text_b_len;
+    uint64_t *d_line_off;            /* n_jobs + 1 */
+    uint8_t *d_out; uint64_t out_cap;
+    uint64_t *d_counters;
+} hsa_sam_merge_batch_t;
+int hsa_sam_merge_device(hsa_index_t *ix, const hsa_sam_merge_batch_t *b, void *stream);
 
 /* ---- FASTQ bytes to a search batch ----
  * bwa_read_seq (bwaseqio.c:161-231) over kseq_read (kseq.h:155-193), and the filter and
