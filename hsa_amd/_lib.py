@@ -39,7 +39,7 @@ EXPORTS = [  # every symbol include/hsa_gpu.h and include/hsa_bwtaln.h declare
     "hsa_index_set_text64_device", "hsa_refine_rows_device64", "hsa_choose_hits_device64",
     "hsa_choose_timing", "hsa_choose_launch_times", "hsa_sam_lines_device64", "hsa_sam_timing", "hsa_splice_lines_device", "hsa_sam_merge_device",
     "hsa_sam_launch_times", "hsa_index_levels", "hsa_reads_device", "hsa_reads_timing",
-    "hsa_reads_launch_times", "hsa_fasta_scratch_bytes", "hsa_fasta_device", "hsa_bwt_files_scratch_bytes",
+    "hsa_reads_launch_times", "hsa_reads_device_opts", "hsa_sam_lines_device64_trim", "hsa_splice_lines_device_trim", "hsa_fasta_scratch_bytes", "hsa_fasta_device", "hsa_bwt_files_scratch_bytes",
     "hsa_bwt_files_device", "hsa_fasta_timing", "hsa_fasta_launch_times", "hsa_bwt_files_launch_times",
 ]
 SP_RES_WORDS = 20  # hsa_splice_match_batch's per-read answer (include/hsa_gpu.h)
@@ -62,7 +62,8 @@ SL_ROW_WORDS = 24
 HSA_SP_MAX_STACKS = 128
 # hsa_reads_device: per-record status, words per record row, the longest read, the bytes of
 # the input per block of the newline passes, the counters
-HSA_RD_SEARCHED, HSA_RD_NDROP, HSA_RD_POLYAT = range(3)
+HSA_RD_SEARCHED, HSA_RD_NDROP, HSA_RD_POLYAT, HSA_RD_FILTERED = range(4)
+RD_OPT_COUNTERS = ("rows", "filtered", "trimmed_bases", "total_bases")       # hsa_reads_device_opts' d_opt_counters
 RD_ROW_WORDS = 4
 HSA_RD_MAX_LEN = 65535
 HSA_RD_TILE = 4096
@@ -207,6 +208,12 @@ class SamBatch64(C.Structure):
                 ("d_out", C.c_void_p), ("out_cap", C.c_uint64), ("d_line_stat", C.c_void_p), ("d_counters", C.c_void_p)]
 
 
+class SamTrim(C.Structure):
+    """hsa_sam_trim_t (include/hsa_gpu.h): the reads' stored lengths and barcodes for the two
+    line writers, device pointers."""
+    _fields_ = [("d_full_len", C.c_void_p), ("d_bc", C.c_void_p), ("bc_len", C.c_uint32)]
+
+
 class SpliceLinesBatch(C.Structure):
     """hsa_splice_lines_batch_t (include/hsa_gpu.h): the batch, hsa_splice_device's results and
     the reads' names and qualities in; the spliced reads' SAM text, its per-read offsets,
@@ -238,7 +245,8 @@ class ReadsBatch(C.Structure):
                 ("regime", C.c_int32), ("trim_qual", C.c_int32), ("mode", C.c_uint32), ("d_jobs", C.c_void_p),
                 ("job_cap", C.c_uint64), ("d_codes", C.c_void_p), ("code_cap", C.c_uint64), ("d_names", C.c_void_p),
                 ("name_cap", C.c_uint64), ("d_name_off", C.c_void_p), ("d_quals", C.c_void_p), ("qual_cap", C.c_uint64),
-                ("d_qual_off", C.c_void_p), ("d_rec", C.c_void_p), ("d_counters", C.c_void_p)]
+                ("d_qual_off", C.c_void_p), ("d_rec", C.c_void_p), ("d_counters", C.c_void_p),
+                ("d_full_len", C.c_void_p), ("d_bc", C.c_void_p), ("rec_cap", C.c_uint32), ("d_opt_counters", C.c_void_p)]
 
 
 class FastaBatch(C.Structure):
@@ -408,6 +416,9 @@ def lib():
     if hasattr(L, "hsa_sam_lines_device64"):        # (older A/B builds lack the SAM lines)
         L.hsa_sam_lines_device64.argtypes = [vp, C.POINTER(SamBatch64), vp]
         L.hsa_sam_timing.argtypes = [C.c_int]
+    if hasattr(L, "hsa_sam_lines_device64_trim"):
+        L.hsa_sam_lines_device64_trim.argtypes = [vp, C.POINTER(SamBatch64), C.POINTER(SamTrim), vp]
+        L.hsa_splice_lines_device_trim.argtypes = [vp, C.POINTER(SpliceLinesBatch), C.POINTER(SamTrim), vp]
     if hasattr(L, "hsa_splice_lines_device"):
         L.hsa_splice_lines_device.argtypes = [vp, C.POINTER(SpliceLinesBatch), vp]
         L.hsa_sam_merge_device.argtypes = [vp, C.POINTER(SamMergeBatch), vp]
@@ -415,6 +426,8 @@ def lib():
         L.hsa_sam_launch_times.argtypes = [vp, f32]
     if hasattr(L, "hsa_reads_device"):              # (older A/B builds lack the FASTQ loader)
         L.hsa_reads_device.argtypes = [vp, C.POINTER(ReadsBatch), vp]
+        if hasattr(L, "hsa_reads_device_opts"):
+            L.hsa_reads_device_opts.argtypes = [vp, C.POINTER(ReadsBatch), vp]
         L.hsa_reads_timing.argtypes = [C.c_int]
         L.hsa_reads_timing.restype = None
         L.hsa_reads_launch_times.argtypes = [vp, f32]
@@ -793,24 +806,32 @@ class GpuIndex:
         check(lib().hsa_choose_launch_times(self._handle(), ms))
         return {k: float(v) for k, v in zip(self.CHOOSE_LAUNCHES, ms)}
 
-    def sam_lines64(self, batch: "SamBatch64", stream=None):
+    def sam_lines64(self, batch: "SamBatch64", stream=None, trim: "SamTrim" = None):
         """hsa_sam_lines_device64: the SAM lines of a batch from the device outputs of
         search_device64, choose_hits64 and refine_rows64 (batch.d_line_off, d_out,
         d_line_stat, d_counters) on `stream` (a hipStream_t address; None: the index's own);
         does not synchronise.  hsa_amd.sam.device_sam drives it.  Without a handle the
-        library answers itself: HSA_E_NODEV where no GPU is visible."""
+        library answers itself: HSA_E_NODEV where no GPU is visible.  trim: the reads' stored
+        lengths and barcodes (hsa_sam_lines_device64_trim), or None."""
         if not hasattr(lib(), "hsa_sam_lines_device64"):
             raise HsaError("this libhsa_gpu.so has no hsa_sam_lines_device64: rebuild it")
-        check(lib().hsa_sam_lines_device64(getattr(self, "h", None), C.byref(batch), stream))
+        if trim is None:
+            check(lib().hsa_sam_lines_device64(getattr(self, "h", None), C.byref(batch), stream))
+        else:
+            check(lib().hsa_sam_lines_device64_trim(getattr(self, "h", None), C.byref(batch), C.byref(trim), stream))
 
-    def splice_lines(self, batch: "SpliceLinesBatch", stream=None):
+    def splice_lines(self, batch: "SpliceLinesBatch", stream=None, trim: "SamTrim" = None):
         """hsa_splice_lines_device: the SAM lines of the spliced reads of a batch from
         splice_device's results (batch.d_rows, d_cigar, d_line_off, d_out, d_line_stat,
         d_counters) on `stream` (a hipStream_t address; None: the index's own); does not
-        synchronise.  hsa_amd.chain.splice_lines drives it."""
+        synchronise.  hsa_amd.chain.splice_lines drives it.  trim: as sam_lines64 takes it
+        (hsa_splice_lines_device_trim)."""
         if not hasattr(lib(), "hsa_splice_lines_device"):
             raise HsaError("this libhsa_gpu.so has no hsa_splice_lines_device: rebuild it")
-        check(lib().hsa_splice_lines_device(getattr(self, "h", None), C.byref(batch), stream))
+        if trim is None:
+            check(lib().hsa_splice_lines_device(getattr(self, "h", None), C.byref(batch), stream))
+        else:
+            check(lib().hsa_splice_lines_device_trim(getattr(self, "h", None), C.byref(batch), C.byref(trim), stream))
 
     def sam_merge(self, batch: "SamMergeBatch", stream=None):
         """hsa_sam_merge_device: the lines of sam_lines64 and of splice_lines over the same
@@ -829,6 +850,13 @@ class GpuIndex:
         if not hasattr(lib(), "hsa_reads_device"):
             raise HsaError("this libhsa_gpu.so has no hsa_reads_device: rebuild it")
         check(lib().hsa_reads_device(getattr(self, "h", None), C.byref(batch), stream))
+
+    def reads_device_opts(self, batch: "ReadsBatch", stream=None):
+        """hsa_reads_device_opts: reads_device with the reader's options of batch.trim_qual and
+        batch.mode (-q, -B, -Y, -I), batch.d_full_len, d_bc, rec_cap and d_opt_counters."""
+        if not hasattr(lib(), "hsa_reads_device_opts"):
+            raise HsaError("this libhsa_gpu.so has no hsa_reads_device_opts: rebuild it")
+        check(lib().hsa_reads_device_opts(getattr(self, "h", None), C.byref(batch), stream))
 
     READS_LAUNCHES = ("count", "tile_scan", "lines", "record", "max_keep", "record_scan", "rows", "bytes")
 

@@ -48,8 +48,17 @@ fixtures have no such read (0 of 601, 614 and 203 reads sent are handed back).  
 header unless --header is given; with it, "@SQ\\tSN:<name>\\tLN:<length>" per chromosome of the
 .ann file, the reference's format (bwt_print_sam_SQ, bwtse.c:826-834).
 
-Not built: quality trimming (-q), barcodes (-B), the Casava filter (-Y), Illumina-1.3
-qualities (-I), BAM input (-b, -0, -1, -2), colour space (-c): refused.  -t is accepted and
+The reader's options are bwa_read_seq's (bwaseqio.c:161-231), on the device for the canonical
+records and in parse_host for the rest: -q INT trims a read's end by quality (bwa_trim_read):
+the search, the refinement and MD see the trimmed read, and the line has the whole read's SEQ
+and QUAL, the trimmed bases as an S op (bwa_correct_trimmed) and XC:i; -B INT cuts a barcode
+off the front (BC:Z); -Y skips the records Casava marks as filtered; -I takes 31 off every
+quality.  A skipped record is no read: it counts towards no batch, gets no line, is not
+written to --unaligned, and is counted as `filtered`; `trimmed_bases` of `total_bases` is what
+the reference reports as "% bases are trimmed".  --unaligned writes a read's record as it was
+given, barcode included.
+
+Not built: BAM input (-b, -0, -1, -2), colour space (-c): refused.  -t is accepted and
 ignored.  A read the choice counts as a zero-draw read (probability 2^-48 per read) stops the
 run with an error."""
 from __future__ import annotations
@@ -67,6 +76,8 @@ from ._lib import (ALN64_WORDS, DRAND48_SEED0, HSA_RD_NDROP, HSA_RD_POLYAT, HSA_
 HSA_DRAND48_SEED0 = DRAND48_SEED0
 BATCH_READS = 0x186A0            # bwtaln.c:477
 MODE_GAPE, MODE_COMPREAD, MODE_LOGGAP, MODE_NONSTOP = 0x01, 0x02, 0x04, 0x10
+MODE_CFY, MODE_IL13 = reads.MODE_CFY, reads.MODE_IL13
+MODE_READER = MODE_CFY | MODE_IL13 | 0xFF000000          # what bwa_read_seq takes of gap_opt_t.mode (the barcode length on top)
 SEED_NONE = reads.SEED_NONE
 TABLE_LEN = HSA_RF_MAX_LEN + 1   # reads past it go through the host parser (and are not refined)
 ONES = 0xFFFFFFFFFFFFFFFF
@@ -98,10 +109,14 @@ def _atof(s: str) -> float:
     return float(m.group(0)) if m else 0.0
 
 
-def parse_options(args):
+def parse_options(args, reader_options=False):
     """bwa_aln's option switch (bwtaln.c:539-575) over `args`: (the option dict, the
     positional arguments, dict(header, unaligned, out)).  Options of what is not built raise
-    ValueError."""
+    ValueError.  reader_options: take the reader's options as the switch sets them (:558,
+    :566-568): -q INT (trim_qual), -B INT (mode |= n << 24), -I (MODE_IL13), -Y (MODE_CFY); a
+    barcode over BWA_MAX_BCLEN (the reference then reads nothing) and a trim_qual over
+    reads.MAX_TRIM_QUAL are ValueError.  Without it they are refused, as before the reader
+    had them; the command line (main) sets it."""
     import getopt
     o = default_opts()
     extra = dict(header=False, unaligned=None, out=None)
@@ -126,6 +141,15 @@ def parse_options(args):
             o["max_top2"] = 0x7FFFFFFF
         elif k == "-q":
             o["trim_qual"] = _atoi(v)
+        elif k == "-B" and reader_options:
+            n = _atoi(v)
+            if not 0 <= n <= reads.BWA_MAX_BCLEN:
+                raise ValueError(f"-B {n}: the maximum barcode length is {reads.BWA_MAX_BCLEN}")
+            o["mode"] |= n << 24
+        elif k == "-I" and reader_options:
+            o["mode"] |= MODE_IL13
+        elif k == "-Y" and reader_options:
+            o["mode"] |= MODE_CFY
         elif k == "-f":
             extra["out"] = v
         elif k == "--header":
@@ -135,12 +159,15 @@ def parse_options(args):
         elif k == "--splice":
             extra["splice"] = True                          # (the key is there only when the option is)
         else:
-            raise ValueError(f"option {k} is not built (barcodes, Casava filter, Illumina-1.3 qualities, BAM, colour space)")
+            raise ValueError(f"option {k} is not built" + (" (BAM input, colour space)" if reader_options else
+                                                           " (barcodes, Casava filter, Illumina-1.3 qualities, BAM, colour space)"))
     if opte > 0:
         o["max_gape"] = opte
         o["mode"] &= ~MODE_GAPE
-    if o["trim_qual"] != 0:
+    if o["trim_qual"] != 0 and not reader_options:
         raise ValueError("quality trimming (-q) is not built")
+    if o["trim_qual"] > reads.MAX_TRIM_QUAL:
+        raise ValueError(f"-q {o['trim_qual']}: at most {reads.MAX_TRIM_QUAL} (the trimming sum of a {0xFFFF}-base read stays in 32 bits)")
     return o, rest, extra
 
 
@@ -225,50 +252,56 @@ def _maxdiff_of(opt):
 
 # ---------------------------------------------------------------- loading a batch
 def _host_segment(p, thr, md_of, seed_len):
-    """The arrays of a parse_host result as the device loader would leave them."""
+    """The arrays of a parse_host result as the device loader would leave them: a read is
+    stored whole, and everything the search sees is of its trimmed length."""
     n = len(p["names"])
     rec = np.zeros((n, 4), np.uint32)
-    jobs, codes, names, quals, has_q = [], [], [], [], []
+    jobs, codes, names, quals, has_q, full, bcs = [], [], [], [], [], [], []
     off = 0
     for k in range(n):
-        sq = p["seqs"][k]
-        nn = int((sq > 3).sum())
-        poly = len(sq) >= 15 and bool((sq[:15] == 0).all() or (sq[:15] == 3).all())
+        sq, ln = p["seqs"][k], p["lens"][k]
+        nn = int((sq[:ln] > 3).sum())
+        poly = ln >= 15 and bool((sq[:15] == 0).all() or (sq[:15] == 3).all())
         st = HSA_RD_NDROP if nn > thr else HSA_RD_POLYAT if poly else HSA_RD_SEARCHED
-        rec[k] = (st, len(sq), nn, len(jobs) if st == HSA_RD_SEARCHED else 0xFFFFFFFF)
+        rec[k] = (st, ln, nn, len(jobs) if st == HSA_RD_SEARCHED else 0xFFFFFFFF)
         if st == HSA_RD_SEARCHED:
-            jobs.append((off, len(sq), md_of(len(sq)), seed_len if seed_len < len(sq) else SEED_NONE, 0))
+            jobs.append((off, ln, md_of(ln), seed_len if seed_len < ln else SEED_NONE, 0))
             off += len(sq)
             codes.append(sq)
             names.append(p["names"][k])
             quals.append(p["quals"][k] or b"")
             has_q.append(p["quals"][k] is not None)
+            full.append(len(sq))
+            bcs.append(p["bcs"][k])
     nb, noff = sam.pack_strings(names)
     qb, qoff = sam.pack_strings(quals)
     return dict(rec=rec, jobs=np.array(jobs, JOB_DTYPE) if jobs else np.zeros(0, JOB_DTYPE),
                 codes=np.concatenate(codes) if codes else np.zeros(0, np.uint8), names=nb, name_off=noff, quals=qb,
-                qual_off=qoff, has_qual=np.array(has_q, bool), max_all=max((len(s) for s in p["seqs"]), default=0))
+                qual_off=qoff, has_qual=np.array(has_q, bool), max_all=max(p["lens"], default=0),
+                full_len=np.array(full, np.uint32), bc=np.frombuffer(b"".join(bcs), np.uint8))
 
 
 def _load_batch(gi, data, pos, opt, d_table, batch_reads, window):
     """Records of `data` from `pos` on, up to batch_reads: (segments in read order, the
     offset after them, the window size to go on with).  A device segment is a load_device
-    result, a host segment a parse_host result."""
+    result, a host segment a parse_host result.  Both readers take the reader's options of opt;
+    a record they skip (the Casava filter, a read not longer than the barcode) does not count."""
     segs, have, host_n = [], 0, 1
+    rd = dict(mode=opt["mode"] & MODE_READER, trim_qual=opt["trim_qual"])
     while have < batch_reads and pos < len(data):
         w = min(len(data) - pos, window)
         at_eof = pos + w == len(data)
         t = reads.load_device(gi, reads.upload(data[pos:pos + w]), w, at_eof, batch_reads - have, opt["max_diff"],
-                              opt["seed_len"], maxdiff=d_table)
+                              opt["seed_len"], maxdiff=d_table, **rd)
         c, got = t["ctr"], t["n_loaded"]
-        if got:
+        if t["n_rows"]:
             segs.append(dict(kind="dev", t=t, span=(pos, w, at_eof, batch_reads - have)))
             have += got
         pos += c["consumed"]
         if c["bad_record"] != ONES:
             host_n = 1 if got else min(2 * host_n, 1 << 20)     # (more at a time while the device takes nothing)
-            p = reads.parse_host(data, min(host_n, batch_reads - have), start=pos)
-            if p["names"]:
+            p = reads.parse_host(data, min(host_n, batch_reads - have), start=pos, **rd)
+            if p["names"] or p["filtered"]:
                 segs.append(dict(kind="host", p=p))
                 have += len(p["names"])
             pos = p["consumed"]
@@ -286,36 +319,48 @@ def _load_batch(gi, data, pos, opt, d_table, batch_reads, window):
 
 def _merge(gi, data, segs, opt, d_table):
     """One device batch of the segments: the tensors of load_device's keys, the per-record
-    rows on the host (job indices of the batch), has_qual per job, the batch's threshold."""
+    rows on the host (job indices of the batch; the records the reader skipped have none),
+    has_qual per job, the batch's threshold; with trimming full_len, with a barcode bc and
+    bc_len (hsa_amd.chain's optional batch keys); the reader's statistics."""
     import torch
+    from ._lib import HSA_RD_FILTERED
     md_of = _maxdiff_of(opt)
-    max_all = max([s["t"]["ctr"]["max_loaded"] if s["kind"] == "dev" else max(len(x) for x in s["p"]["seqs"]) for s in segs])
+    rd = dict(mode=opt["mode"] & MODE_READER, trim_qual=opt["trim_qual"])
+    bc_len = rd["mode"] >> 24
+    max_all = max([s["t"]["ctr"]["max_loaded"] if s["kind"] == "dev" else max(s["p"]["lens"], default=0) for s in segs])
     thr = md_of(max_all)                                   # local_opt.max_diff, bwtaln.c:273-274
     dev = chain.to_device
     parts = []
+    reader = dict(filtered=0, trimmed_bases=0, total_bases=0)
     for s in segs:
         if s["kind"] == "dev":
-            t, n_rec = s["t"], s["t"]["n_loaded"]
+            t, n_rec = s["t"], s["t"]["n_rows"]
             rec = t["rec"][:4 * n_rec].cpu().numpy().view(np.uint32).reshape(-1, 4).copy()
             if opt["fnr"] > 0 and t["ctr"]["threshold"] != (thr & ONES) and \
                     ((rec[:, 0] == HSA_RD_NDROP) & (rec[:, 2].astype(np.int64) <= thr)).any():
                 pos, w, at_eof, room = s["span"]           # the chunk alone set a narrower threshold
                 if max_all < TABLE_LEN:
                     t = reads.load_device(gi, reads.upload(data[pos:pos + w]), w, at_eof, room, opt["max_diff"], opt["seed_len"],
-                                          maxdiff=d_table, len_floor=max_all)
-                    assert t["n_loaded"] == n_rec and t["ctr"]["threshold"] == (thr & ONES)
+                                          maxdiff=d_table, len_floor=max_all, **rd)
+                    assert t["n_rows"] == n_rec and t["ctr"]["threshold"] == (thr & ONES)
                     rec = t["rec"][:4 * n_rec].cpu().numpy().view(np.uint32).reshape(-1, 4).copy()
                 else:
-                    s = dict(kind="host", p=reads.parse_host(data[pos:pos + t["ctr"]["consumed"]], n_rec))
+                    s = dict(kind="host", p=reads.parse_host(data[pos:pos + t["ctr"]["consumed"]], t["n_loaded"], **rd))
         if s["kind"] == "dev":
             c, n = t["ctr"], t["n_jobs"]
-            parts.append(dict(rec=rec, n=n, jobs=t["jobs"][:n * JOB_DTYPE.itemsize], codes=t["codes"][:c["code_wanted"] - 16],
+            reader["filtered"] += t["octr"]["filtered"]
+            reader["trimmed_bases"] += t["octr"]["trimmed_bases"]
+            reader["total_bases"] += t["octr"]["total_bases"]
+            rec = rec[rec[:, 0] != HSA_RD_FILTERED]
+            parts.append(dict(rec=rec, n=n, full_len=t["full_len"][:n], bc=t["bc"][:n * bc_len], jobs=t["jobs"][:n * JOB_DTYPE.itemsize], codes=t["codes"][:c["code_wanted"] - 16],
                               names=t["names"][:c["name_wanted"]], quals=t["quals"][:c["qual_wanted"]],
                               name_off=t["name_off"][:n + 1], qual_off=t["qual_off"][:n + 1], has_qual=np.ones(n, bool)))
         else:
             h = _host_segment(s["p"], thr, md_of, opt["seed_len"])
             n = len(h["jobs"])
-            parts.append(dict(rec=h["rec"], n=n, jobs=dev(h["jobs"]), codes=dev(h["codes"]), names=dev(h["names"]),
+            for k in reader:
+                reader[k] += s["p"][k]
+            parts.append(dict(rec=h["rec"], n=n, full_len=dev(h["full_len"]), bc=dev(h["bc"]), jobs=dev(h["jobs"]), codes=dev(h["codes"]), names=dev(h["names"]),
                               quals=dev(h["quals"]), name_off=dev(h["name_off"]), qual_off=dev(h["qual_off"]),
                               has_qual=h["has_qual"]))
     jobs, name_off, qual_off, recs = [], [], [], []
@@ -335,7 +380,14 @@ def _merge(gi, data, segs, opt, d_table):
     pad = torch.zeros(64, dtype=torch.uint8, device="cuda")
     rec = np.concatenate(recs)
     kept = rec[rec[:, 0] == HSA_RD_SEARCHED, 1]
-    return dict(jobs=torch.cat(jobs + [pad[:24]]), codes=torch.cat([p["codes"] for p in parts] + [pad]),
+    extra = dict(reader=reader)
+    full = torch.cat([p["full_len"].view(torch.int32) for p in parts] + [pad[:4].view(torch.int32)])
+    extra["max_full"] = int(full[:nj].max().item()) if nj else 0
+    if opt["trim_qual"] >= 1:                               # (without the options the writers run their plain entry points)
+        extra["full_len"] = full
+    if bc_len:
+        extra.update(bc=torch.cat([p["bc"] for p in parts] + [pad[:1]]), bc_len=bc_len)
+    return dict(extra, jobs=torch.cat(jobs + [pad[:24]]), codes=torch.cat([p["codes"] for p in parts] + [pad]),
                 names=torch.cat([p["names"] for p in parts] + [pad[:1]]), quals=torch.cat([p["quals"] for p in parts] + [pad[:1]]),
                 name_off=torch.cat(name_off + [end(nb)]), qual_off=torch.cat(qual_off + [end(qb)]), n_jobs=nj, rec=rec,
                 has_qual=np.concatenate([p["has_qual"] for p in parts]), thr=thr, max_all=max_all,
@@ -392,10 +444,10 @@ def _splice_lines(gi, b, s, first, cnt, chrs, has_qual, opt, stats):
     noff = b["name_off"][first:first + cnt + 1].cpu().numpy().view(np.uint64)
     max_name = int(np.diff(noff.astype(np.int64)).max()) if cnt else 0
     stride = 33                                             # two segments' ops and the N
-    max_line = max(1, sam.line_bound(max_name, b["max_len"], chrs["max_chr"], stride, 0, 0))
+    max_line = max(1, sam.line_bound(max_name, b["max_full"], chrs["max_chr"], stride, 0, 0, "full_len" in b, b.get("bc_len", 0)))
     ks = first - s["sp_first"]
     n_two = int((s["res"][ks * SP_RES_WORDS:(ks + cnt) * SP_RES_WORDS].view(cnt, SP_RES_WORDS)[:, 1] == 2).sum())
-    cap = n_two * (max_name + 2 * b["max_len"] + chrs["max_chr"] + 200) + 64
+    cap = n_two * (max_name + 2 * b["max_full"] + chrs["max_chr"] + b.get("bc_len", 0) + 200) + 64
     o, ctr = chain.splice_lines(gi, b, s, first, cnt, strings, chrs["n"], max_line, cap, cigar_stride=stride,
                                 max_top2=opt["max_top2"], comp_read=bool(opt["mode"] & MODE_COMPREAD))
     stat = o["stat"].cpu().numpy().view(np.uint32)[:cnt]
@@ -539,8 +591,12 @@ def align_fastq(gi, chr_names, data_or_path, opts, out, batch_reads=BATCH_READS,
     import torch
     data = _read_input(data_or_path)
     opt = dict(opts)
-    if opt.get("trim_qual", 0) != 0 or opt["mode"] & ~(MODE_GAPE | MODE_COMPREAD | MODE_LOGGAP | MODE_NONSTOP):
-        raise ValueError("quality trimming, barcodes, the Casava filter, Illumina-1.3 qualities and BAM input are not built")
+    opt.setdefault("trim_qual", 0)
+    if opt["mode"] & ~(MODE_GAPE | MODE_COMPREAD | MODE_LOGGAP | MODE_NONSTOP | MODE_READER):
+        raise ValueError("BAM input is not built")
+    if (opt["mode"] >> 24) > reads.BWA_MAX_BCLEN or opt["trim_qual"] > reads.MAX_TRIM_QUAL:
+        raise ValueError(f"a barcode of at most {reads.BWA_MAX_BCLEN} bases, trim_qual at most {reads.MAX_TRIM_QUAL}")
+    rd = dict(mode=opt["mode"] & MODE_READER, trim_qual=opt["trim_qual"])
     if not opt["mode"] & MODE_COMPREAD:
         raise ValueError("colour-space reads (-c) are not built")
     if splice:
@@ -550,7 +606,7 @@ def align_fastq(gi, chr_names, data_or_path, opts, out, batch_reads=BATCH_READS,
             raise ValueError(f"the splice path with more than {HSA_SP_MAX_STACKS} score buckets is not built")
     d_table = torch.from_numpy(_table(opt["fnr"])).cuda() if opt["fnr"] > 0 else None
     stats = collections.Counter(reads=0, searched=0, searched_again=0, n_drop=0, polyat=0, n_drop_after_switch=0, lines=0,
-                                refused=0, batches=0, device_records=0, host_records=0)
+                                refused=0, batches=0, device_records=0, host_records=0, filtered=0, trimmed_bases=0, total_bases=0)
     if splice:
         stats.update(spliced_sent=0, spliced=0, spliced_unspliced=0, spliced_no_pair=0, handed_back=0, spliced_multi=0,
                      spliced_refused=0)
@@ -567,19 +623,21 @@ def align_fastq(gi, chr_names, data_or_path, opts, out, batch_reads=BATCH_READS,
         stats["reads"] += len(rec)
         stats["n_drop"] += int((rec[:, 0] == HSA_RD_NDROP).sum())
         stats["polyat"] += int((rec[:, 0] == HSA_RD_POLYAT).sum())
+        stats.update(b["reader"])                           # (a Counter: adds)
         stats["device_records"] += sum(s["t"]["n_loaded"] for s in segs if s["kind"] == "dev")
         stats["host_records"] += sum(len(s["p"]["names"]) for s in segs if s["kind"] == "host")
         state, has_line = _run_batch(gi, chr_names, b, opt, out, state, stats, splice=splice)
         if unaligned is not None:
-            p = reads.parse_host(data[start:pos], len(rec))
+            p = reads.parse_host(data[start:pos], len(rec), **rd)
             assert len(p["names"]) == len(rec)
             for r in range(len(rec)):
                 if rec[r, 0] == HSA_RD_SEARCHED and has_line[int(rec[r, 3])]:
                     continue
-                if p["quals"][r] is None:
-                    unaligned.write(b">" + p["names"][r] + b"\n" + p["raw"][r] + b"\n")
+                seq, qual = p["orig"][r]                     # the record as given: barcode and quality offset included
+                if qual is None:
+                    unaligned.write(b">" + p["names"][r] + b"\n" + seq + b"\n")
                 else:
-                    unaligned.write(b"@" + p["names"][r] + b"\n" + p["raw"][r] + b"\n+\n" + p["quals"][r] + b"\n")
+                    unaligned.write(b"@" + p["names"][r] + b"\n" + seq + b"\n+\n" + qual + b"\n")
     stats["no_line"] = stats["reads"] - stats["lines"]
     return state, dict(stats)
 
@@ -593,7 +651,7 @@ def sam_header(prefix: str) -> bytes:
 def main(argv=None) -> int:
     argv = sys.argv[1:] if argv is None else argv
     try:
-        opts, rest, extra = parse_options(argv)
+        opts, rest, extra = parse_options(argv, reader_options=True)
     except Exception as e:                                  # getopt's and ours
         print(f"hsa_amd.align: {e}", file=sys.stderr)
         return 1
@@ -615,6 +673,8 @@ def main(argv=None) -> int:
         if extra["out"]:
             out.close()
         gi.close()
+    if opts["trim_qual"] >= 1 and stats["total_bases"]:       # bwaseqio.c:224-225
+        print(f"[hsa_amd.align] {100.0 * stats['trimmed_bases'] / stats['total_bases']:.1f}% bases are trimmed.", file=sys.stderr)
     print("[hsa_amd.align] " + ", ".join(f"{k} {v}" for k, v in stats.items() if k != "refused_names"), file=sys.stderr)
     return 0
 

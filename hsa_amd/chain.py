@@ -10,6 +10,10 @@ outputs added, so the dict of the last stage holds the whole chain:
 
   the batch       jobs (hsa_job_t rows as bytes), codes (padded: _lib.pad_codes), n_jobs,
                   max_len; a sub-range of a batch is the same keys with offset views;
+                  optional, for trimmed reads and barcodes (hsa_amd.reads.load_device with
+                  the reader's options): full_len (u32 per job: the stored length, jobs' len
+                  being the trimmed one), bc and bc_len (bc_len bytes per job).  trim_views
+                  cuts them for a sub-range and sam_trim hands them to the two line writers;
   search          n_aln, flags, hit_off, hits, sc (the 16 counters), hit_cap, first (the
                   batch's job the arrays start at);
   positions       pos_off, pos, pos_hit, pos_ctr (optional for the SAM lines), pos_cap:
@@ -30,7 +34,8 @@ import numpy as np
 
 from . import reads
 from ._lib import (ALN64_WORDS, HSA_RF_MAX_LEN, HSA_RF_MD, JOB_DTYPE, RF_ROW_WORDS, SL_ROW_WORDS, SP_RES_WORDS, ChooseBatch64,
-                   DeviceBatch, HitPosBatch64, HsaError, RefineBatch64, SamBatch64, SamMergeBatch, SpliceBatch, SpliceLinesBatch,
+                   DeviceBatch, HitPosBatch64, HsaError, RefineBatch64, SamBatch64, SamMergeBatch, SamTrim, SpliceBatch,
+                   SpliceLinesBatch,
                    anchor_regime, ext_regime, regime_of)
 
 N_MULTI = 3                      # bwtaln.c:514
@@ -81,11 +86,30 @@ def _ptr(d, k):
     return d[k].data_ptr() if d.get(k) is not None else None
 
 
-def _call(fn, *args):
+def _call(fn, *args, **kw):
     import torch
     torch.cuda.synchronize()
-    fn(*args)
+    fn(*args, **kw)
     torch.cuda.synchronize()
+
+
+def trim_views(b, first):
+    """The batch's optional keys of trimmed reads and barcodes (full_len, bc, bc_len) from job
+    `first` on: what a sub-range's dict takes over.  Empty for a batch without them."""
+    o = {}
+    if b.get("full_len") is not None:
+        o["full_len"] = b["full_len"][first:]
+    if b.get("bc_len"):
+        o.update(bc=b["bc"][first * b["bc_len"]:], bc_len=b["bc_len"])
+    return o
+
+
+def sam_trim(d):
+    """The SamTrim (hsa_sam_trim_t) of a dict's full_len / bc / bc_len, or None without them:
+    the line writers then run their plain entry points."""
+    if d.get("full_len") is None and not d.get("bc_len"):
+        return None
+    return SamTrim(d_full_len=_ptr(d, "full_len"), d_bc=_ptr(d, "bc") if d.get("bc_len") else None, bc_len=int(d.get("bc_len") or 0))
 
 
 # ---------------------------------------------------------------- search
@@ -146,7 +170,8 @@ def choose64_batch(b, t, first, n, state, n_multi=N_MULTI):
     sub = dict(jobs=b["jobs"][first * JOB_DTYPE.itemsize:], codes=b["codes"], n_aln=t["n_aln"][k:], hit_off=t["hit_off"][k:],
                hits=t["hits"], n_jobs=n, max_len=b["max_len"], sel=_new(max(n, 1) * 4, "int32"),
                sel64=_new(max(n, 1) * 4, "int64"), rng=_new(1, "int64"), pos_off=_new(n + 1, "int64"),
-               pos=_new(cap * 4, "int64"), pos_hit=_new(cap, "int32"), pos_ctr=_new(8, "int64"), pos_cap=cap)
+               pos=_new(cap * 4, "int64"), pos_hit=_new(cap, "int32"), pos_ctr=_new(8, "int64"), pos_cap=cap,
+               **trim_views(b, first))
     cb = ChooseBatch64(d_jobs=sub["jobs"].data_ptr(), n_jobs=n, d_n_aln=sub["n_aln"].data_ptr(),
                        d_hit_off=sub["hit_off"].data_ptr(), d_hits=sub["hits"].data_ptr(), n_multi=n_multi, rng_state=state,
                        d_sel=sub["sel"].data_ptr(), d_sel64=sub["sel64"].data_ptr(), d_rng_out=sub["rng"].data_ptr(),
@@ -256,7 +281,7 @@ def splice_lines(gi, b, s, first, n, strings, n_chr, max_line, out_cap, **kw):
     output tensors, the counters as 8 u64 on the host)."""
     for _ in range(2):
         lb, o = splice_lines_batch(b, s, first, n, strings, n_chr, max_line, out_cap, **kw)
-        _call(gi.splice_lines, lb)
+        _call(gi.splice_lines, lb, trim=sam_trim(trim_views(b, first)))
         ctr = o["ctr"].cpu().numpy().view(np.uint64)
         if int(ctr[0]) <= int(ctr[1]):
             break
@@ -311,7 +336,7 @@ def sam_lines64(gi, dev, strings, n_chr, max_line, out_cap, **kw):
     tensors, the counters as 8 u64 on the host)."""
     for _ in range(2):
         sb, o = sam_lines64_batch(dev, strings, n_chr, max_line, out_cap, **kw)
-        _call(gi.sam_lines64, sb)
+        _call(gi.sam_lines64, sb, trim=sam_trim(dev))
         ctr = o["ctr"].cpu().numpy().view(np.uint64)
         if int(ctr[0]) <= int(ctr[1]):
             break

@@ -80,9 +80,14 @@
 // depend on the record alone, which is the same in all 64 lanes, so no lane enters a region
 // alone.  The other kernels' loops hold no barrier and no cross-lane operation.
 //
-// Not built: quality trimming (-q, bwa_trim_read: needs full_len and the XC tag
-// downstream), barcodes (-B), the Casava filter (-Y), Illumina-1.3 qualities (-I), BAM input
-// (-b): non-zero values of those options are HSA_E_ARG.
+// The reader's options (bwaseqio.c:176-211) come through hsa_reads_device_opts, the same code
+// with k_rd_record and k_rd_bytes instantiated with OPT: the Casava filter (-Y), Illumina-1.3
+// qualities (-I), barcodes (-B) and quality trimming (-q, bwa_trim_read as a wave-wide scan:
+// rd_trim).  A trimmed read keeps its bytes: hsa_job_t.len is the trimmed length, d_full_len
+// the stored one.  With a filter one more scan (the records the reader keeps) and k_rd_limit
+// end the load behind the max_records-th kept record.  hsa_reads_device refuses the options
+// (HSA_E_ARG) and then runs the same code.  Not built: BAM input (-b).
+#include <algorithm>
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
@@ -92,7 +97,16 @@
 
 #define RD_ONES32 0xFFFFFFFFu
 #define RD_RT 16u                      // records per wavefront of k_rd_record and k_rd_bytes
-#define RD_REFUSED_MODE 0xFF0003E8u   // barcode length, IL13, BAM*, CFY (bwtaln.h:122-131)
+#define RD_REFUSED_MODE 0xFF0003E8u   // barcode length, IL13, BAM*, CFY (bwtaln.h:122-131): hsa_reads_device takes none
+#define RD_MODE_CFY 0x08u             // bwtaln.h:125
+#define RD_MODE_IL13 0x200u           // :131
+#define RD_MODE_BAM 0x1E0u            // :127-130: not built
+#define RD_MAX_BCLEN 63u              // BWA_MAX_BCLEN, bwtaln.h:28
+#define RD_MIN_RDLEN 35u              // BWA_MIN_RDLEN, bwtaln.h:26
+// bwa_trim_read's sum: a byte of 33..127, 31 off with IL13, gives q - 33 in -31..94, so a
+// step adds between trim_qual - 94 and trim_qual + 31 and |s| <= HSA_RD_MAX_LEN * (trim_qual + 94)
+#define RD_MAX_TRIM ((int32_t)(0x7FFFFFFFu / HSA_RD_MAX_LEN) - 94)
+#define RD_FL_FILTERED 0x80u          // r_fl between k_rd_record and k_rd_keep: the reader skips the record
 
 struct Rd3 {
     uint64_t j, c, n;       // jobs, code bytes, name bytes
@@ -117,6 +131,12 @@ struct RdArgs {
     uint32_t *tile_cnt, *tile_base, *ls, *g;   // g: [0] first non-canonical record, [1] longest loaded, [2] longest kept
     uint32_t *r_len, *r_nn, *r_fl, *r_name_len;
     Rd3 *s_in, *s_out;
+    // the reader's options (hsa_reads_device_opts); all zero / null without them
+    int32_t trim_qual;                         // bwa_trim_read's, or 0
+    uint32_t qshift, bc_len, casava, max_rec;  // 31 with IL13; mode >> 24; the CFY bit; max_records
+    uint32_t *full_len; uint8_t *bc;           // per job: the length before trimming, the barcode
+    unsigned long long *octr;
+    uint32_t *r_full, *unf, *unf_scan;         // scratch: full length; 1 for a record the reader keeps, and its scan
 };
 
 // The newlines among the 16 bytes at the aligned address of unit u, as a bit mask; bytes
@@ -171,7 +191,12 @@ __device__ __forceinline__ RdShape rd_shape(const RdArgs &a)
     s.cand = full < a.M ? (uint32_t)full : a.M;
     return s;
 }
-__device__ __forceinline__ uint32_t rd_loaded(const RdArgs &a, const RdShape &s) { return a.g[0] < s.cand ? a.g[0] : s.cand; }
+// (g[3]: the record after the max_records-th one the reader keeps, k_rd_limit; all-ones without a filter)
+__device__ __forceinline__ uint32_t rd_loaded(const RdArgs &a, const RdShape &s)
+{
+    const uint32_t n = a.g[0] < s.cand ? a.g[0] : s.cand;
+    return a.g[3] < n ? a.g[3] : n;
+}
 
 __global__ void __launch_bounds__(256) k_rd_lines(RdArgs a)
 {
@@ -204,12 +229,92 @@ __device__ __forceinline__ uint32_t rd_code(uint32_t c)
     return l == 'a' ? 0u : l == 'c' ? 1u : l == 'g' ? 2u : l == 't' ? 3u : c == '-' ? 5u : 4u;
 }
 
+// The inclusive sum and the maximum over a wavefront's 64 lanes; every lane calls.
+__device__ __forceinline__ int32_t rd_wave_scan(int32_t v, uint32_t lane)
+{
+#pragma unroll
+    for (uint32_t d = 1u; d < 64u; d <<= 1) {
+        const int32_t t = __shfl_up(v, d, 64);
+        if (lane >= d) v += t;
+    }
+    return v;
+}
+__device__ __forceinline__ int32_t rd_wave_max(int32_t v)
+{
+#pragma unroll
+    for (uint32_t d = 32u; d; d >>= 1) {
+        const int32_t t = __shfl_xor(v, (int)d, 64);
+        v = t > v ? t : v;
+    }
+    return v;
+}
+
+// The Casava filter (bwaseqio.c:176-181) on a comment of n bytes: it is a C string, so a NUL
+// before the first ':' ends the search; the byte after that ':' must be 'Y'.  Called by the
+// whole wave with the same c and n.
+__device__ __forceinline__ bool rd_casava(const uint8_t *c, uint32_t n, uint32_t lane)
+{
+    for (uint32_t p0 = 0; p0 < n; p0 += 64u) {
+        const uint32_t p = p0 + lane;
+        const uint32_t b = p < n ? c[p] : 1u;
+        const unsigned long long colon = __ballot(b == (uint32_t)':'), nul = __ballot(b == 0u);
+        if (colon | nul) {
+            const uint32_t first = (uint32_t)__ffsll((long long)(colon | nul)) - 1u;
+            const uint32_t at = p0 + first + 1u;
+            return ((colon >> first) & 1ull) && at < n && c[at] == (uint8_t)'Y';
+        }
+    }
+    return false;
+}
+
+// bwa_trim_read (bwaseqio.c:92-103) on the quality bytes q[0, len), qshift taken off each:
+// the length the read keeps.  The reference walks l from len - 1 down to RD_MIN_RDLEN with
+// s += trim_qual - (q[l] - 33), ends at the first s < 0, and cuts at the l of the first
+// strictly greater s.  Here 64 steps of the walk at a time, lane i at step p0 + i: a
+// wave-wide inclusive sum on top of the carried one gives every step's s, a ballot the
+// first negative one (the steps from there on do not count), a maximum over the steps
+// before it the chunk's best s, and the lowest lane that holds it the largest l of equal
+// maxima.  The carry (sum, best, best_l) and the trip count are the same in all lanes.
+// |s| <= len * (trim_qual + 94) fits int32 for trim_qual <= RD_MAX_TRIM.
+__device__ __forceinline__ uint32_t rd_trim(const uint8_t *q, uint32_t len, int32_t trim_qual, uint32_t qshift, uint32_t lane)
+{
+    if (len <= RD_MIN_RDLEN) return len;
+    const uint32_t steps = len - RD_MIN_RDLEN;
+    int32_t sum = 0, best = 0;
+    uint32_t best_l = len;
+    for (uint32_t p0 = 0; p0 < steps; p0 += 64u) {
+        const uint32_t p = p0 + lane;
+        const bool on = p < steps;
+        const uint32_t l = len - 1u - (on ? p : 0u);          // (a lane without a step loads the last byte)
+        const int32_t qv = (int32_t)q[l] - (int32_t)qshift - 33;
+        const int32_t s = sum + rd_wave_scan(on ? trim_qual - qv : 0, lane);
+        const unsigned long long neg = __ballot(on && s < 0);
+        const uint32_t stop = neg ? (uint32_t)__ffsll((long long)neg) - 1u : 64u;
+        const bool counts = on && lane < stop;
+        const int32_t top = rd_wave_max(counts ? s : (int32_t)0x80000000);
+        const unsigned long long at_top = __ballot(counts && s == top);
+        if (top > best) {
+            best = top;
+            best_l = len - (p0 + (uint32_t)__ffsll((long long)at_top));      // len - 1 - step
+        }
+        if (neg) break;
+        sum = __shfl(s, 63, 64);
+    }
+    return best_l;
+}
+
 // One wavefront per RD_RT consecutive records, the lanes along the bytes of a record's
 // lines: consecutive lanes load consecutive bytes, and what a record's decisions need of
 // them (a byte that is not allowed, the first white space of the header, the codes above 3,
 // the first 15 codes) comes back as wave-wide ballots.  The record, and so every trip
 // count and every branch around a ballot, is the same in all 64 lanes.
-__global__ void __launch_bounds__(64) k_rd_record(RdArgs a)
+//
+// OPT: the reader's options, in bwa_read_seq's order (bwaseqio.c:176-211): the Casava filter
+// on the comment; the barcode off the front of lines 1 and 3 (a read not longer than it is
+// filtered); bwa_trim_read on the shifted quality; then the codes above 3 and the poly test
+// over the trimmed read, the only length the search sees.  Lines 1 and 3 are validated whole
+// and raw first.  Without OPT none of that code is in the kernel.
+template <bool OPT> __global__ void __launch_bounds__(64) k_rd_record(RdArgs a)
 {
     const uint32_t lane = threadIdx.x;
     const RdShape sh = rd_shape(a);
@@ -222,11 +327,13 @@ __global__ void __launch_bounds__(64) k_rd_record(RdArgs a)
         const uint32_t e0 = s1 - 1u, e1 = s2 - 1u, e2 = s3 - 1u, e3 = s4 - 1u;
         bool bad = false;
         uint32_t name_len = 0, len = e1 - s1, nn = 0, poly = 0;
+        uint32_t full = len, filtered = 0;                  // (OPT: the length before trimming; a record the reader skips)
         // line 0
         if (e0 - s0 < 2u || in[s0] != (uint8_t)'@') bad = true;
         else {
             const uint32_t most = e0 - s0 - 1u > HSA_RD_MAX_LEN ? HSA_RD_MAX_LEN + 1u : e0 - s0 - 1u;
             name_len = most;
+            uint32_t comment = e0;                          // where the comment starts: behind the name's white space
             for (uint32_t p0 = 0; p0 < most; p0 += 64u) {
                 const uint32_t p = p0 + lane;
                 const uint32_t c = p < most ? in[s0 + 1u + p] : 1u;              // (1: neither white space nor NUL)
@@ -235,10 +342,13 @@ __global__ void __launch_bounds__(64) k_rd_record(RdArgs a)
                     const uint32_t first = (uint32_t)__ffsll((long long)sp) - 1u;
                     if (nul & ((1ull << first) - 1ull)) bad = true;
                     name_len = p0 + first;
+                    comment = s0 + 2u + name_len;
                     break;
                 }
                 if (nul) bad = true;
             }
+            if constexpr (OPT)
+                if (a.casava && comment < e0 && rd_casava(in + comment, e0 - comment, lane)) filtered = 1u;
             if (name_len == 0u || name_len > HSA_RD_MAX_LEN) bad = true;
             else if (name_len > 2u && in[s0 + name_len - 1u] == (uint8_t)'/' &&
                      (in[s0 + name_len] == (uint8_t)'1' || in[s0 + name_len] == (uint8_t)'2'))
@@ -246,7 +356,31 @@ __global__ void __launch_bounds__(64) k_rd_record(RdArgs a)
         }
         // lines 1 and 3
         if (len < 1u || len > HSA_RD_MAX_LEN || e3 - s3 != len || (a.maxdiff && len >= a.n_maxdiff)) bad = true;
-        else {
+        else if constexpr (OPT) {
+            for (uint32_t p0 = 0; p0 < len; p0 += 64u) {    // both lines whole, as given
+                const uint32_t p = p0 + lane;
+                const uint32_t c = p < len ? in[s1 + p] : (uint32_t)'A', q = p < len ? in[s3 + p] : (uint32_t)'I';
+                if (__ballot(c < 33u || c > 126u || c == '>' || c == '+' || c == '@' || q < 33u || q > 127u)) bad = true;
+            }
+            if (len <= a.bc_len) filtered = 1u;             // bwaseqio.c:185
+            else if (!bad) {
+                const uint32_t c1 = s1 + a.bc_len, c3 = s3 + a.bc_len;             // the read behind its barcode
+                full = len - a.bc_len;
+                len = a.trim_qual >= 1 ? rd_trim(in + c3, full, a.trim_qual, a.qshift, lane) : full;
+                unsigned long long not_a = 0, not_t = 0;
+                for (uint32_t p0 = 0; p0 < len; p0 += 64u) {
+                    const uint32_t p = p0 + lane;
+                    const bool on = p < len;
+                    const uint32_t code = rd_code(on ? in[c1 + p] : (uint32_t)'A');
+                    nn += (uint32_t)__popcll(__ballot(on && code > 3u));
+                    if (p0 == 0u) {
+                        not_a = __ballot(lane < 15u && (!on || code != 0u));
+                        not_t = __ballot(lane < 15u && (!on || code != 3u));
+                    }
+                }
+                poly = len >= 15u && (not_a == 0ull || not_t == 0ull);
+            }
+        } else {
             unsigned long long not_a = 0, not_t = 0;
             for (uint32_t p0 = 0; p0 < len; p0 += 64u) {
                 const uint32_t p = p0 + lane;
@@ -266,9 +400,24 @@ __global__ void __launch_bounds__(64) k_rd_record(RdArgs a)
         if (e2 - s2 < 1u || in[s2] != (uint8_t)'+') bad = true;
         if (lane == 0u) {
             a.r_len[k] = len; a.r_nn[k] = nn; a.r_fl[k] = poly; a.r_name_len[k] = name_len;
+            if constexpr (OPT) {
+                a.r_full[k] = full;
+                if (filtered) a.r_fl[k] = RD_FL_FILTERED;
+                if (a.unf) a.unf[k] = filtered ? 0u : 1u;
+            }
             if (bad) atomicMin(&a.g[0], k);
         }
     }
+}
+
+// With a filter (the Casava one, a barcode) the records the reader skips do not count
+// towards max_records (bwaseqio.c:221 counts n_seqs): the load ends behind the record that is
+// the max_records-th it keeps.  unf_scan is the exclusive scan of unf, so one lane at most
+// finds its record to be that one.
+__global__ void __launch_bounds__(256) k_rd_limit(RdArgs a)
+{
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k < a.M && a.unf[k] && a.unf_scan[k] + 1u == a.max_rec) a.g[3] = k + 1u;
 }
 
 __global__ void __launch_bounds__(256) k_rd_max(RdArgs a)
@@ -277,7 +426,7 @@ __global__ void __launch_bounds__(256) k_rd_max(RdArgs a)
     if (threadIdx.x == 0) sMax = 0u;
     __syncthreads();
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    if (k < rd_loaded(a, rd_shape(a))) atomicMax(&sMax, a.r_len[k]);
+    if (k < rd_loaded(a, rd_shape(a)) && a.r_fl[k] != RD_FL_FILTERED) atomicMax(&sMax, a.r_len[k]);
     __syncthreads();
     if (threadIdx.x == 0 && sMax) atomicMax(&a.g[1], sMax);
 }
@@ -290,24 +439,35 @@ __device__ __forceinline__ int32_t rd_threshold(const RdArgs &a)
 
 __global__ void __launch_bounds__(256) k_rd_keep(RdArgs a)
 {
-    __shared__ uint32_t sMax;
-    if (threadIdx.x == 0) sMax = 0u;
+    __shared__ uint32_t sMax, sTrim, sTotal;               // (a block's bases: 256 reads of at most 65 535)
+    if (threadIdx.x == 0) sMax = sTrim = sTotal = 0u;
     __syncthreads();
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     if (k <= a.M) {
         Rd3 v{0, 0, 0};
         if (k < rd_loaded(a, rd_shape(a))) {
-            const uint32_t st = (int64_t)a.r_nn[k] > (int64_t)rd_threshold(a) ? HSA_RD_NDROP : a.r_fl[k] ? HSA_RD_POLYAT : HSA_RD_SEARCHED;
+            const uint32_t fl = a.r_fl[k], len = a.r_len[k];
+            const uint32_t full = a.r_full ? a.r_full[k] : len;             // the code and quality bytes stay whole
+            const uint32_t st = fl == RD_FL_FILTERED ? HSA_RD_FILTERED : (int64_t)a.r_nn[k] > (int64_t)rd_threshold(a) ? HSA_RD_NDROP
+                                : fl ? HSA_RD_POLYAT : HSA_RD_SEARCHED;
             a.r_fl[k] = st;
             if (st == HSA_RD_SEARCHED) {
-                v = Rd3{1u, a.r_len[k], a.r_name_len[k]};
-                atomicMax(&sMax, a.r_len[k]);
+                v = Rd3{1u, full, a.r_name_len[k]};
+                atomicMax(&sMax, len);
+            }
+            if (a.octr && st != HSA_RD_FILTERED) {                          // bwaseqio.c:204, :210: every read returned
+                atomicAdd(&sTotal, full);
+                if (full != len) atomicAdd(&sTrim, full - len);
             }
         }
         a.s_in[k] = v;
     }
     __syncthreads();
     if (threadIdx.x == 0 && sMax) atomicMax(&a.g[2], sMax);
+    if (threadIdx.x == 0 && sTotal) {                                       // (sums: any order gives the same)
+        atomicAdd(&a.octr[3], (unsigned long long)sTotal);
+        if (sTrim) atomicAdd(&a.octr[2], (unsigned long long)sTrim);
+    }
 }
 
 __global__ void __launch_bounds__(256) k_rd_rows(RdArgs a)
@@ -321,7 +481,8 @@ __global__ void __launch_bounds__(256) k_rd_rows(RdArgs a)
         const Rd3 at = a.s_out[k];
         const bool kept = st == HSA_RD_SEARCHED;
         uint32_t *row = a.rec + (size_t)HSA_RD_ROW_WORDS * k;
-        row[0] = st; row[1] = len; row[2] = a.r_nn[k]; row[3] = kept ? (uint32_t)at.j : RD_ONES32;
+        const bool skipped = st == HSA_RD_FILTERED;          // (no read: no length, no count)
+        row[0] = st; row[1] = skipped ? 0u : len; row[2] = skipped ? 0u : a.r_nn[k]; row[3] = kept ? (uint32_t)at.j : RD_ONES32;
         if (kept && at.j <= a.job_cap) {
             a.name_off[at.j] = at.n;
             a.qual_off[at.j] = at.c;
@@ -332,6 +493,7 @@ __global__ void __launch_bounds__(256) k_rd_rows(RdArgs a)
                 jb.seed_len = a.seed_len < (int32_t)len ? a.seed_len : 0x7fffffff;        // :332
                 jb.regime = a.regime;
                 a.jobs[at.j] = jb;
+                if (a.full_len) a.full_len[at.j] = a.r_full ? a.r_full[k] : len;
             }
         }
     }
@@ -344,8 +506,10 @@ __global__ void __launch_bounds__(256) k_rd_rows(RdArgs a)
         const bool term = a.n == 0u || a.in[a.n - 1u] == (uint8_t)'\n';
         const uint64_t lines = (uint64_t)nl + (term ? 0u : 1u);
         unsigned long long *c = a.ctr;
+        const uint32_t read = a.unf ? a.unf_scan[loaded] : loaded;        // the records the reader did not skip
         c[0] = loaded + (has_bad ? 1u : 0u);
-        c[1] = loaded;
+        c[1] = read;
+        if (a.octr) { a.octr[0] = loaded; a.octr[1] = loaded - read; }
         c[2] = tot.j; c[3] = tot.j < a.job_cap ? tot.j : a.job_cap;
         c[4] = tot.c + 16u; c[5] = c[4] < a.code_cap ? c[4] : a.code_cap;
         c[6] = tot.n; c[7] = tot.n < a.name_cap ? tot.n : a.name_cap;
@@ -362,7 +526,11 @@ __global__ void __launch_bounds__(256) k_rd_rows(RdArgs a)
 // bytes of a kept record's name, sequence and quality.  Consecutive lanes load consecutive
 // input bytes and store consecutive output bytes (a wave's store covers 64 contiguous bytes
 // of one array); a byte at or past its array's capacity is not stored.
-__global__ void __launch_bounds__(64) k_rd_bytes(RdArgs a)
+//
+// OPT: the read lies behind its barcode, its bytes are those of the whole read (trimming
+// moves hsa_job_t.len alone), the quality loses qshift, and the barcode's bases go to d_bc at
+// stride bc_len, in lower case where the shifted quality is under 13 (bwaseqio.c:188-190).
+template <bool OPT> __global__ void __launch_bounds__(64) k_rd_bytes(RdArgs a)
 {
     const uint32_t lane = threadIdx.x;
     const uint32_t loaded = rd_loaded(a, rd_shape(a));
@@ -376,8 +544,15 @@ __global__ void __launch_bounds__(64) k_rd_bytes(RdArgs a)
         if (k >= loaded) break;                             // (the whole wave)
         if (a.r_fl[k] != HSA_RD_SEARCHED) continue;
         const Rd3 at = a.s_out[k];
-        const uint32_t len = a.r_len[k], nl = a.r_name_len[k];
-        const uint32_t s0 = a.ls[4u * k] + 1u, s1 = a.ls[4u * k + 1u], s3 = a.ls[4u * k + 3u];
+        const uint32_t len = OPT ? a.r_full[k] : a.r_len[k], nl = a.r_name_len[k];
+        const uint32_t bcn = OPT ? a.bc_len : 0u, qshift = OPT ? a.qshift : 0u;
+        const uint32_t s0 = a.ls[4u * k] + 1u, s1 = a.ls[4u * k + 1u] + bcn, s3 = a.ls[4u * k + 3u] + bcn;
+        if constexpr (OPT)
+            if (lane < bcn && at.j < a.job_cap) {           // (bc_len <= 63: one lane per base)
+                const uint32_t c = in[s1 - bcn + lane], q = in[s3 - bcn + lane] - qshift;
+                const bool low = (int32_t)q - 33 < 13;
+                a.bc[at.j * bcn + lane] = (uint8_t)(low ? (c >= 'A' && c <= 'Z' ? c | 0x20u : c) : (c >= 'a' && c <= 'z' ? c & ~0x20u : c));
+            }
         const uint32_t most = len > nl ? len : nl;
         for (uint32_t p0 = 0; p0 < most; p0 += 64u) {
             const uint32_t p = p0 + lane;
@@ -385,7 +560,7 @@ __global__ void __launch_bounds__(64) k_rd_bytes(RdArgs a)
             const uint32_t c = in[s1 + (p < len ? p : 0u)], q = in[s3 + (p < len ? p : 0u)], m = in[s0 + (p < nl ? p : 0u)];
             if (p < len) {
                 if (at.c + p < a.code_cap) a.codes[at.c + p] = (uint8_t)rd_code(c);
-                if (at.c + p < a.qual_cap) a.quals[at.c + p] = (uint8_t)q;
+                if (at.c + p < a.qual_cap) a.quals[at.c + p] = (uint8_t)(q - qshift);
             }
             if (p < nl && at.n + p < a.name_cap) a.names[at.n + p] = (uint8_t)m;
         }
@@ -400,7 +575,17 @@ extern "C" int hsa_reads_launch_times(hsa_index_t *ix, float *ms) { return hsa_s
 
 extern "C" int hsa_reads_device(hsa_index_t *ix, const hsa_reads_batch_t *b, void *stream)
 {
-    const char *what = "hsa_reads_device";
+    if (ix && b && (b->trim_qual != 0 || (b->mode & RD_REFUSED_MODE))) {
+        hsa_set_error("hsa_reads_device: quality trimming, barcodes, the Casava filter and Illumina-1.3 qualities are "
+                      "hsa_reads_device_opts'; BAM input is not built");
+        return HSA_E_ARG;
+    }
+    return hsa_reads_device_opts(ix, b, stream);
+}
+
+extern "C" int hsa_reads_device_opts(hsa_index_t *ix, const hsa_reads_batch_t *b, void *stream)
+{
+    const char *what = "hsa_reads_device_opts";
     if (!ix) {
         int nd = 0;
         if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) { hsa_set_error("%s: no HIP device visible", what); return HSA_E_NODEV; }
@@ -418,18 +603,32 @@ extern "C" int hsa_reads_device(hsa_index_t *ix, const hsa_reads_batch_t *b, voi
         hsa_set_error("%s: n_in under 2^32 - 256, max_records in 1..2^28, at_eof 0 or 1, len_floor inside the table", what);
         return HSA_E_ARG;
     }
-    if (b->trim_qual != 0 || (b->mode & RD_REFUSED_MODE)) {
-        hsa_set_error("%s: quality trimming, barcodes, the Casava filter, Illumina-1.3 qualities and BAM input are not built", what);
+    const uint32_t bc_len = b->mode >> 24;
+    const bool filter = (b->mode & RD_MODE_CFY) != 0u || bc_len != 0u;
+    const bool opt = filter || b->trim_qual >= 1 || (b->mode & RD_MODE_IL13) != 0u;
+    if (b->mode & RD_MODE_BAM) {
+        hsa_set_error("%s: BAM input is not built", what);
+        return HSA_E_ARG;
+    }
+    if (b->trim_qual > RD_MAX_TRIM || bc_len > RD_MAX_BCLEN || b->rec_cap > (1u << 28)) {
+        hsa_set_error("%s: trim_qual at most %d (the walk's sum stays in 32 bits), a barcode of at most %u bases, rec_cap at most 2^28",
+                      what, RD_MAX_TRIM, RD_MAX_BCLEN);
+        return HSA_E_ARG;
+    }
+    if ((b->trim_qual >= 1 && !b->d_full_len) || (bc_len && b->job_cap && !b->d_bc)) {
+        hsa_set_error("%s: trimming needs d_full_len, a barcode d_bc", what);
         return HSA_E_ARG;
     }
     HSA_HIP(hipSetDevice(ix->device));
     hipStream_t st = hsa_stage_stream(stream, ix->stream);
-    RdArgs A;
+    RdArgs A{};
     A.in = b->d_in; A.n = (uint32_t)b->n_in;
     A.lead = b->n_in ? (uint32_t)(reinterpret_cast<uintptr_t>(b->d_in) & 15u) : 0u;
     A.ntiles = (uint32_t)(((uint64_t)A.lead + A.n + HSA_RD_TILE - 1u) / HSA_RD_TILE);
     const uint64_t most = b->n_in / 8u + 1u;                // (the shortest record has 8 bytes)
-    A.M = (uint32_t)(most < b->max_records ? most : b->max_records);
+    // (with a filter the rows of d_rec bound the records looked at, and max_records those the reader keeps)
+    const uint32_t rows = filter && b->rec_cap ? b->rec_cap : b->max_records;
+    A.M = (uint32_t)(most < rows ? most : rows);
     A.ls_last = 4u * A.M + 1u;
     A.at_eof = b->at_eof; A.max_diff = b->max_diff; A.seed_len = b->seed_len; A.regime = b->regime;
     A.maxdiff = b->d_maxdiff; A.n_maxdiff = b->n_maxdiff; A.len_floor = b->len_floor;
@@ -437,7 +636,11 @@ extern "C" int hsa_reads_device(hsa_index_t *ix, const hsa_reads_batch_t *b, voi
     A.names = b->d_names; A.name_cap = b->name_cap; A.name_off = b->d_name_off;
     A.quals = b->d_quals; A.qual_cap = b->qual_cap; A.qual_off = b->d_qual_off;
     A.rec = b->d_rec; A.ctr = (unsigned long long *)b->d_counters;
-    size_t tmp1 = 0, tmp2 = 0;
+    A.trim_qual = b->trim_qual >= 1 ? b->trim_qual : 0; A.qshift = (b->mode & RD_MODE_IL13) ? 31u : 0u;
+    A.bc_len = bc_len; A.casava = b->mode & RD_MODE_CFY; A.max_rec = b->max_records;
+    A.full_len = b->d_full_len; A.bc = b->d_bc; A.octr = (unsigned long long *)b->d_opt_counters;
+    size_t tmp1 = 0, tmp2 = 0, tmp3 = 0;
+    if (filter) HSA_TRY(hsa_scan_bytes(tmp3, 0u, (size_t)A.M + 1, rocprim::plus<uint32_t>(), st));
     HSA_TRY(hsa_scan_bytes(tmp1, 0u, (size_t)A.ntiles + 1, rocprim::plus<uint32_t>(), st));
     HSA_TRY(hsa_scan_bytes(tmp2, Rd3{0, 0, 0}, (size_t)A.M + 1, Rd3Plus(), st));
     void *d_tmp = nullptr;
@@ -452,7 +655,12 @@ extern "C" int hsa_reads_device(hsa_index_t *ix, const hsa_reads_batch_t *b, voi
         A.r_name_len = c.take<uint32_t>(A.M);
         A.s_in = c.take<Rd3>((size_t)A.M + 1);
         A.s_out = c.take<Rd3>((size_t)A.M + 1);
-        d_tmp = c.take<char>(tmp1 > tmp2 ? tmp1 : tmp2);
+        if (opt) A.r_full = c.take<uint32_t>(A.M);
+        if (filter) {
+            A.unf = c.take<uint32_t>((size_t)A.M + 1);
+            A.unf_scan = c.take<uint32_t>((size_t)A.M + 1);
+        }
+        d_tmp = c.take<char>(std::max(tmp1, std::max(tmp2, tmp3)));
         return c.bytes();
     };
     HSA_TRY(hsa_grow(&ix->d_rd, &ix->d_rd_cap, layout(Carver())));
@@ -462,6 +670,9 @@ extern "C" int hsa_reads_device(hsa_index_t *ix, const hsa_reads_batch_t *b, voi
     HSA_TRY(tm.mark(0, st));
     HSA_HIP(hipMemsetAsync(A.g, 0xFF, 4, st));               // no non-canonical record yet
     HSA_HIP(hipMemsetAsync(A.g + 1, 0, 28, st));
+    HSA_HIP(hipMemsetAsync(A.g + 3, 0xFF, 4, st));           // no limit by the records the reader keeps
+    if (filter) HSA_HIP(hipMemsetAsync(A.unf, 0, ((size_t)A.M + 1) * 4, st));
+    if (A.octr) HSA_HIP(hipMemsetAsync(A.octr, 0, HSA_RD_OPT_COUNTERS * sizeof(uint64_t), st));
     HSA_HIP(hipMemsetAsync(A.tile_cnt + A.ntiles, 0, 4, st));
     // (a line start the input does not reach is never read; zeroed so that no run depends on an earlier one)
     HSA_HIP(hipMemsetAsync(A.ls, 0, ((size_t)A.ls_last + 1) * 4, st));
@@ -476,9 +687,15 @@ extern "C" int hsa_reads_device(hsa_index_t *ix, const hsa_reads_batch_t *b, voi
     HSA_HIP(hipGetLastError());
     HSA_TRY(tm.mark(3, st));
     const unsigned rb = (A.M + 1u + 255u) / 256u, wb = (A.M + RD_RT - 1u) / RD_RT;
-    hipLaunchKernelGGL(k_rd_record, dim3(wb), dim3(64), 0, st, A);
+    if (opt) hipLaunchKernelGGL(k_rd_record<true>, dim3(wb), dim3(64), 0, st, A);
+    else hipLaunchKernelGGL(k_rd_record<false>, dim3(wb), dim3(64), 0, st, A);
     HSA_HIP(hipGetLastError());
     HSA_TRY(tm.mark(4, st));
+    if (filter) {
+        HSA_HIP(rocprim::exclusive_scan(d_tmp, tmp3, A.unf, A.unf_scan, 0u, (size_t)A.M + 1, rocprim::plus<uint32_t>(), st));
+        hipLaunchKernelGGL(k_rd_limit, dim3(rb), dim3(256), 0, st, A);
+        HSA_HIP(hipGetLastError());
+    }
     hipLaunchKernelGGL(k_rd_max, dim3(rb), dim3(256), 0, st, A);
     HSA_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_rd_keep, dim3(rb), dim3(256), 0, st, A);
@@ -489,7 +706,8 @@ extern "C" int hsa_reads_device(hsa_index_t *ix, const hsa_reads_batch_t *b, voi
     hipLaunchKernelGGL(k_rd_rows, dim3(rb), dim3(256), 0, st, A);
     HSA_HIP(hipGetLastError());
     HSA_TRY(tm.mark(7, st));
-    hipLaunchKernelGGL(k_rd_bytes, dim3(wb), dim3(64), 0, st, A);
+    if (opt) hipLaunchKernelGGL(k_rd_bytes<true>, dim3(wb), dim3(64), 0, st, A);
+    else hipLaunchKernelGGL(k_rd_bytes<false>, dim3(wb), dim3(64), 0, st, A);
     HSA_HIP(hipGetLastError());
     HSA_TRY(tm.mark(8, st));
     tm.end();

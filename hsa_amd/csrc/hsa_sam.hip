@@ -78,7 +78,15 @@ struct SamArgs {
     uint32_t *stat;
     unsigned long long *ctr;
     uint64_t *lens;                        // scratch: n_jobs + 1
+    // trimmed reads and barcodes (hsa_sam_trim_t); null / 0: every read is whole, no barcode
+    const uint32_t *full_len;
+    const uint8_t *bc;
+    uint32_t bc_len;
 };
+
+// The stored length of read j: SEQ and QUAL are printed over it (bwtse.c:738-749), while
+// hsa_job_t.len, what the search saw, is the XC tag's clip_len.
+__device__ __forceinline__ uint32_t sm_full_len(const SamArgs &a, uint32_t j, uint32_t len) { return a.full_len ? a.full_len[j] : len; }
 
 __device__ __forceinline__ uint64_t sm_n_rows(const SamArgs &a)
 {
@@ -128,7 +136,8 @@ template <class S> __device__ __forceinline__ void sm_emit(const SamArgs &a, uin
     mk.name_len = (uint32_t)(a.name_off[j + 1] - mk.name_src);
     mk.code_off = jb.off;
     mk.qual_off = a.quals ? a.qual_off[j] : 0;
-    mk.len = jb.len;
+    const uint32_t full = sm_full_len(a, j, jb.len);
+    mk.len = full;
     mk.strand = strand;
     mk.name_dst = s.pos();
     s.skip(mk.name_len);
@@ -136,13 +145,15 @@ template <class S> __device__ __forceinline__ void sm_emit(const SamArgs &a, uin
     s.ch('\t'); sm_chr(a, r0, s);
     s.ch('\t'); s.dec(a.rpos[2 * r0 + 1]);
     s.ch('\t'); s.dec(mapq);
-    s.ch('\t'); sm_cigar(a, r0, s);
+    s.ch('\t');                                                         // the chosen row's CIGAR alone is corrected (:637)
+    sm_cigar_clipped(a.cigar + (size_t)a.cigar_stride * r0, a.rows[HSA_RF_ROW_WORDS * r0 + 1], strand, full - jb.len, s);
     s.lit("\t*\t0\t0\t");                                               // :720
     mk.seq_dst = s.pos();
-    s.skip(jb.len);
+    s.skip(full);
     s.ch('\t');
     mk.qual_dst = a.quals ? s.pos() : 0xFFFFFFFFu;                      // (all-ones: no QUAL to copy)
-    if (a.quals) s.skip(jb.len); else s.ch('*');
+    if (a.quals) s.skip(full); else s.ch('*');
+    sm_clip_tags(a.bc ? a.bc + (size_t)a.bc_len * j : nullptr, a.bc_len, jb.len, full, s);
     s.lit("\tXT:A:"); s.ch(typ == 1u ? 'U' : 'R');                      // :762
     s.ch('\t'); s.ch(a.comp_read ? 'N' : 'C'); s.lit("M:i:"); s.dec(a.rows[HSA_RF_ROW_WORDS * r0 + 2]);
     s.lit("\tX0:i:"); s.dec(c1);
@@ -219,10 +230,11 @@ __device__ __forceinline__ uint32_t sm_status(const SamArgs &a, uint32_t j, uint
     if (refused) return HSA_SAM_REFINE;
     if (bad) return HSA_SAM_INPUT;
     const hsa_job_t jb = a.jobs[j];
-    if (a.name_off[j + 1] < a.name_off[j] || a.name_off[j + 1] - a.name_off[j] > a.max_line || jb.len > a.max_line)
+    const uint32_t full = sm_full_len(a, j, jb.len);
+    if (a.name_off[j + 1] < a.name_off[j] || a.name_off[j + 1] - a.name_off[j] > a.max_line || full > a.max_line || full < jb.len)
         return HSA_SAM_INPUT;                      // (lengths past max_line: no line can hold them)
-    if (a.quals && (a.qual_off[j + 1] < a.qual_off[j] || a.qual_off[j + 1] - a.qual_off[j] != jb.len)) return HSA_SAM_INPUT;
-    return sm_bad_codes(a.codes + jb.off, jb.len) ? HSA_SAM_INPUT : HSA_SAM_OK;
+    if (a.quals && (a.qual_off[j + 1] < a.qual_off[j] || a.qual_off[j + 1] - a.qual_off[j] != full)) return HSA_SAM_INPUT;
+    return sm_bad_codes(a.codes + jb.off, full) ? HSA_SAM_INPUT : HSA_SAM_OK;
 }
 
 // The counters are summed per block first: a million lanes adding to one address take
@@ -387,6 +399,11 @@ extern "C" int hsa_sam_launch_times(hsa_index_t *ix, float *ms) { return hsa_sta
 
 extern "C" int hsa_sam_lines_device64(hsa_index_t *ix, const hsa_sam_batch64_t *b, void *stream)
 {
+    return hsa_sam_lines_device64_trim(ix, b, nullptr, stream);
+}
+
+extern "C" int hsa_sam_lines_device64_trim(hsa_index_t *ix, const hsa_sam_batch64_t *b, const hsa_sam_trim_t *trim, void *stream)
+{
     const char *what = "hsa_sam_lines_device64";
     if (!ix) {
         int nd = 0;
@@ -408,6 +425,10 @@ extern "C" int hsa_sam_lines_device64(hsa_index_t *ix, const hsa_sam_batch64_t *
     }
     if ((b->d_quals == nullptr) != (b->d_qual_off == nullptr)) {
         hsa_set_error("%s: d_quals and d_qual_off go together", what);
+        return HSA_E_ARG;
+    }
+    if (trim && (trim->bc_len > HSA_SAM_MAX_BC || (trim->bc_len != 0u) != (trim->d_bc != nullptr))) {
+        hsa_set_error("%s: a barcode of 1..%u bytes per read goes with d_bc", what, HSA_SAM_MAX_BC);
         return HSA_E_ARG;
     }
     if (b->max_line < 1u || b->max_line > HSA_SAM_MAX_LINE) {
@@ -443,6 +464,7 @@ extern "C" int hsa_sam_lines_device64(hsa_index_t *ix, const hsa_sam_batch64_t *
     A.lds_text = (A.tile * b->max_line + 16u + 15u) & ~15u;
     A.line_off = b->d_line_off; A.out = b->d_out; A.out_cap = b->out_cap; A.stat = b->d_line_stat;
     A.ctr = (unsigned long long *)b->d_counters;
+    A.full_len = trim ? trim->d_full_len : nullptr; A.bc = trim ? trim->d_bc : nullptr; A.bc_len = trim ? trim->bc_len : 0u;
     StageTimer &tm = ix->sm_t;                 // records only when hsa_sam_timing asked for it
     HSA_TRY(tm.begin(g_sam_timing != 0));
     HSA_TRY(tm.mark(0, st));

@@ -62,3 +62,27 @@ __device__ __forceinline__ uint32_t sm_op_letter(uint32_t op)
     // "MIDNSHP=X" (bwtse.c:713): eight letters in a word, X apart
     return op < 8u ? (uint32_t)(0x3D504853'4E44494Dull >> (8u * op)) & 0xFFu : (uint32_t)'X';
 }
+
+// A CIGAR of n ops with bwa_correct_trimmed applied while it is printed (bwtse.c:496-534): the
+// `clip` bases that trimming took off the read's end join a last S op on the forward strand
+// and a first one on the reverse strand, or are an S op of their own there (a read without
+// a CIGAR is "<len>M" in `ops` already).  clip == 0: the ops as they are.
+template <class S> __device__ __forceinline__ void sm_cigar_clipped(const uint32_t *ops, uint32_t n, uint32_t strand, uint32_t clip, S &s)
+{
+    if (clip && strand && (n == 0u || (ops[0] >> 28) != 4u)) { s.dec(clip); s.ch('S'); }
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t w = ops[i], op = w >> 28;
+        const bool edge = clip && op == 4u && i == (strand ? 0u : n - 1u);
+        s.dec((uint64_t)(w & 0x0FFFFFFFu) + (edge ? clip : 0u));
+        s.ch((char)sm_op_letter(op));
+    }
+    if (clip && !strand && (n == 0u || (ops[n - 1u] >> 28) != 4u)) { s.dec(clip); s.ch('S'); }
+}
+
+// The tags between QUAL and XT (bwtse.c:755-758): BC:Z with the read's barcode, XC:i with
+// clip_len where the read was trimmed
+template <class S> __device__ __forceinline__ void sm_clip_tags(const uint8_t *bc, uint32_t bc_len, uint32_t len, uint32_t full, S &s)
+{
+    if (bc && bc_len) { s.lit("\tBC:Z:"); s.bytes(bc, bc_len); }
+    if (len < full) { s.lit("\tXC:i:"); s.dec(len); }
+}

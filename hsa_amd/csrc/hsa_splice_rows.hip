@@ -59,6 +59,7 @@ struct SlArgs {
     int32_t max_top2, comp_read;
     uint32_t max_len, max_line, cigar_stride;
     uint32_t *rows, *cigar;
+    const uint32_t *full_len; const uint8_t *bc; uint32_t bc_len;      // hsa_sam_trim_t; null / 0 without
     uint64_t *line_off;
     uint8_t *out;
     uint64_t out_cap;
@@ -212,6 +213,9 @@ __global__ void __launch_bounds__(64) k_sl_pair(SlArgs a)
     }
 }
 
+// The stored length of read j (hsa_sam_trim_t): SEQ and QUAL are printed over it, the segments lie in hsa_job_t.len
+__device__ __forceinline__ uint32_t sl_full_len(const SlArgs &a, uint32_t j, uint32_t len) { return a.full_len ? a.full_len[j] : len; }
+
 // The merged CIGAR (:578-582) into d_cigar, the row words after the end rules; HSA_SL_OK or
 // why not.
 __device__ __forceinline__ uint32_t sl_merge(const SlArgs &a, uint32_t j)
@@ -248,9 +252,10 @@ __device__ __forceinline__ uint32_t sl_merge(const SlArgs &a, uint32_t j)
     const uint64_t c = row[6];
     if (a.chr_off[c + 1] < a.chr_off[c] || a.chr_off[c + 1] - a.chr_off[c] > a.max_line) return HSA_SL_INPUT;
     const hsa_job_t jb = a.jobs[j];
-    if (a.name_off[j + 1] < a.name_off[j] || a.name_off[j + 1] - a.name_off[j] > a.max_line || jb.len > a.max_line)
+    const uint32_t full = sl_full_len(a, j, jb.len);
+    if (a.name_off[j + 1] < a.name_off[j] || a.name_off[j + 1] - a.name_off[j] > a.max_line || full > a.max_line || full < jb.len)
         return HSA_SL_INPUT;
-    if (a.quals && (a.qual_off[j + 1] < a.qual_off[j] || a.qual_off[j + 1] - a.qual_off[j] != jb.len)) return HSA_SL_INPUT;
+    if (a.quals && (a.qual_off[j + 1] < a.qual_off[j] || a.qual_off[j + 1] - a.qual_off[j] != full)) return HSA_SL_INPUT;
     return HSA_SL_OK;
 }
 
@@ -265,6 +270,7 @@ template <class S> __device__ __forceinline__ void sl_emit(const SlArgs &a, uint
 {
     const uint32_t *row = a.rows + (size_t)HSA_SL_ROW_WORDS * j;
     const uint32_t len = a.jobs[j].len, strand = row[4], c1 = row[3];
+    const uint32_t full = sl_full_len(a, j, len);
     mk.name_len = (uint32_t)(a.name_off[j + 1] - a.name_off[j]);
     mk.name_dst = s.pos();
     s.skip(mk.name_len);
@@ -275,13 +281,14 @@ template <class S> __device__ __forceinline__ void sl_emit(const SlArgs &a, uint
     s.ch('\t'); s.dec(row[7]);
     s.lit("\t0\t");                                        // mapQ: the value of :345 is dropped
     const uint32_t *cg = a.cigar + (size_t)a.cigar_stride * j;
-    for (uint32_t i = 0; i < row[5]; ++i) { s.dec(cg[i] & 0x0FFFFFFFu); s.ch((char)sm_op_letter(cg[i] >> 28)); }
+    sm_cigar_clipped(cg, row[5], strand, full - len, s);     // bwa_correct_trimmed holds for a spliced read too (bwtse.c:637)
     s.lit("\t*\t0\t0\t");
     mk.seq_dst = s.pos();
-    s.skip(len);
+    s.skip(full);
     s.ch('\t');
     mk.qual_dst = s.pos();
-    if (a.quals) s.skip(len); else s.ch('*');
+    if (a.quals) s.skip(full); else s.ch('*');
+    sm_clip_tags(a.bc ? a.bc + (size_t)a.bc_len * j : nullptr, a.bc_len, len, full, s);
     s.lit("\tXT:A:S\t"); s.ch(a.comp_read ? 'N' : 'C'); s.lit("M:i:0");      // nm is never computed for these reads
     s.lit("\tX0:i:"); s.dec(c1);
     if (a.max_top2 >= 0 && c1 <= (uint32_t)a.max_top2) { s.lit("\tX1:i:"); s.dec(c1); }     // c2 = c1, :315
@@ -346,8 +353,9 @@ __global__ void __launch_bounds__(64) k_sl_write(SlArgs a)
         const uint64_t letters = strand ? SM_REV : SM_FWD;
         const uint8_t *code = a.codes + jb.off;
         const uint8_t *qual = a.quals ? a.quals + a.qual_off[j] : nullptr;
-        for (uint32_t k = lane; k < jb.len; k += 64u) {
-            const uint32_t i = strand ? jb.len - 1u - k : k;
+        const uint32_t full = sl_full_len(a, j, jb.len);
+        for (uint32_t k = lane; k < full; k += 64u) {
+            const uint32_t i = strand ? full - 1u - k : k;
             const uint32_t c = code[i];
             if (mk.seq_dst + k < cap) g[mk.seq_dst + k] = (uint8_t)(letters >> (8u * (c < 4u ? c : 4u)));
             if (qual && mk.qual_dst + k < cap) g[mk.qual_dst + k] = qual[i];
@@ -356,6 +364,12 @@ __global__ void __launch_bounds__(64) k_sl_write(SlArgs a)
 }
 
 extern "C" int hsa_splice_lines_device(hsa_index_t *ix, const hsa_splice_lines_batch_t *b, void *stream)
+{
+    return hsa_splice_lines_device_trim(ix, b, nullptr, stream);
+}
+
+extern "C" int hsa_splice_lines_device_trim(hsa_index_t *ix, const hsa_splice_lines_batch_t *b, const hsa_sam_trim_t *trim,
+                                            void *stream)
 {
     const char *what = "hsa_splice_lines_device";
     if (!ix) { hsa_set_error("%s: null handle", what); return HSA_E_ARG; }
@@ -368,6 +382,10 @@ extern "C" int hsa_splice_lines_device(hsa_index_t *ix, const hsa_splice_lines_b
                       !b->d_rows || !b->d_line_stat || (b->cigar_stride && !b->d_cigar) ||
                       (b->n_chr && (!b->d_chr_names || !b->d_chr_off)))) {
         hsa_set_error("%s: null argument", what);
+        return HSA_E_ARG;
+    }
+    if (trim && (trim->bc_len > HSA_SAM_MAX_BC || (trim->bc_len != 0u) != (trim->d_bc != nullptr))) {
+        hsa_set_error("%s: a barcode of 1..%u bytes per read goes with d_bc", what, HSA_SAM_MAX_BC);
         return HSA_E_ARG;
     }
     if ((b->d_quals == nullptr) != (b->d_qual_off == nullptr)) {
@@ -416,6 +434,7 @@ extern "C" int hsa_splice_lines_device(hsa_index_t *ix, const hsa_splice_lines_b
     A.flag = b->flag; A.max_top2 = b->max_top2; A.comp_read = b->comp_read;
     A.max_len = (uint32_t)b->max_len; A.max_line = b->max_line; A.cigar_stride = b->cigar_stride;
     A.rows = b->d_rows; A.cigar = b->d_cigar;
+    A.full_len = trim ? trim->d_full_len : nullptr; A.bc = trim ? trim->d_bc : nullptr; A.bc_len = trim ? trim->bc_len : 0u;
     A.line_off = b->d_line_off; A.out = b->d_out; A.out_cap = b->out_cap; A.stat = b->d_line_stat;
     A.ctr = (unsigned long long *)b->d_counters;
     HSA_HIP(hipMemsetAsync(b->d_counters, 0, 8 * sizeof(uint64_t), st));

@@ -15,8 +15,10 @@ Two ways to the same bytes:
 spliced_line is the same restatement for a spliced read (type BWA_TYPE_SPLICING, XT:A:S):
 the text hsa_splice_lines_device (hsa_amd/csrc/hsa_splice_rows.hip) is tested against.
 
-Not printed: RG / BC / XC tags (no read group, barcode or trimmed read reaches the 64-bit
-path) and the XA list of a spliced read with more than one pair."""
+A trimmed read (bwa aln -q) and a barcode (-B) reach both: SEQ and QUAL over the whole read,
+bwa_correct_trimmed on the line's own CIGAR, BC:Z and XC:i behind QUAL.  Not printed: the RG
+tag (no read group reaches the 64-bit path) and the XA list of a spliced read with more than
+one pair."""
 from __future__ import annotations
 
 import numpy as np
@@ -34,8 +36,28 @@ def _record(rec):
     return w0 & 0xFFFF, (w0 >> 16) & 0xFF, (w0 >> 24) & 0xFF, (w1 >> 30) & 3
 
 
+def clipped_cigar(ops, strand, clip) -> str:
+    """The CIGAR column of bwa_cigar_t words `ops` after bwa_correct_trimmed (bwtse.c:496-534):
+    the `clip` bases trimming took off join a last S op on the forward strand, a first one on
+    the reverse strand, or are an S op of their own there."""
+    ops = [(int(w) >> 28, int(w) & 0x0FFFFFFF) for w in np.asarray(ops, np.uint32).reshape(-1)]
+    if clip:
+        at = 0 if strand else len(ops) - 1
+        if ops and ops[at][0] == 4:
+            ops[at] = (4, ops[at][1] + clip)
+        else:
+            ops.insert(0 if strand else len(ops), (4, clip))
+    return "".join(f"{l}{CIGAR_OPS[op]}" for op, l in ops)
+
+
+def clip_tags(clip_len, full_len, bc) -> list:
+    """The tags between QUAL and XT (bwtse.c:755-758)."""
+    out = [f"BC:Z:{bc.decode('latin-1') if isinstance(bc, bytes) else bc}"] if bc else []
+    return out + ([f"XC:i:{clip_len}"] if clip_len < full_len else [])
+
+
 def sam_line(name, seq_codes, qual, chr_names, sel, sel64, rows, rpos, cigar, md, pos, hits, max_top2=30,
-             flag=0, comp_read=True) -> str:
+             flag=0, comp_read=True, clip_len=None, bc=None) -> str:
     """One line, without the newline.
 
     seq_codes: the read as it was given (codes 0-4); qual: its quality string or None;
@@ -43,7 +65,8 @@ def sam_line(name, seq_codes, qual, chr_names, sel, sel64, rows, rpos, cigar, md
     md, pos: the read's rows of the refinement and of the position arrays, chosen row
     first; hits: the hit record of each of those rows (d_hits[d_hit_off[j] + d_pos_hit[t]]);
     max_top2: gap_opt_t.max_top2 (X1 is printed when X0 <= max_top2); comp_read:
-    BWA_MODE_COMPREAD (NM, else CM)."""
+    BWA_MODE_COMPREAD (NM, else CM).  clip_len: the length the read was trimmed to and searched
+    with (bwa aln -q; seq_codes and qual stay whole), or None; bc: its barcode (-B), or None."""
     typ, _, mapq, n_xa = (int(v) for v in np.asarray(sel).reshape(-1)[:4])
     _, c1, c2, _ = (int(v) for v in np.asarray(sel64).reshape(-1)[:4])
     if typ not in (1, 2):
@@ -58,12 +81,17 @@ def sam_line(name, seq_codes, qual, chr_names, sel, sel64, rows, rpos, cigar, md
         raise ValueError(f"the chosen row was not answered (status {main['status']})")
     if strand:
         flag |= SAM_FSR
-    out = [name, str(flag), chr_names[int(pos[0][1])], str(int(rpos[0][1])), str(mapq), main["cigar"], "*", "0", "0"]
+    full = len(seq_codes)
+    clip_len = full if clip_len is None else int(clip_len)
+    n_cigar = int(np.asarray(rows[0], np.uint32).reshape(-1)[1])
+    text = clipped_cigar(np.asarray(cigar[0]).reshape(-1)[:n_cigar], strand, full - clip_len) if clip_len < full else main["cigar"]
+    out = [name, str(flag), chr_names[int(pos[0][1])], str(int(rpos[0][1])), str(mapq), text, "*", "0", "0"]
     if strand == 0:
         out.append("".join(SEQ_FWD[c] for c in seq_codes))
     else:
         out.append("".join(SEQ_REV[c] for c in seq_codes[::-1]))
     out.append("*" if qual is None else (qual[::-1] if strand else qual))
+    out += clip_tags(clip_len, full, bc)
     out += [f"XT:A:{XT[typ]}", f"{'NM' if comp_read else 'CM'}:i:{main['nm']}", f"X0:i:{c1}"]
     if c1 <= max_top2:
         out.append(f"X1:i:{c2}")
@@ -87,7 +115,7 @@ CIGAR_OPS = "MIDNSHP=X"      # bwtse.c:713
 
 
 def spliced_line(name, seq_codes, qual, chr_name, ori_pos, cigar, strand, c1, c2, n_mm, max_top2=30, flag=0,
-                 comp_read=True) -> str:
+                 comp_read=True, clip_len=None, bc=None) -> str:
     """The line of a spliced read (bwa_print_sam1 for type BWA_TYPE_SPLICING, bwtse.c:677-799),
     without the newline.
 
@@ -96,17 +124,21 @@ def spliced_line(name, seq_codes, qual, chr_name, ori_pos, cigar, strand, c1, c2
     res_aln[0]'s; c1, c2: the capped row count bwt_aln2pos_splicing leaves in both
     (bwtse.c:310-315); n_mm: mm of segment 0 plus mm of segment 1 (:594).  mapQ is 0 (the
     value of :345 is dropped), NM is 0 (nm is never computed for these reads), XO and XG are
-    0 (gap is never set), and there is no MD."""
+    0 (gap is never set), and there is no MD.  clip_len, bc: as sam_line takes them (the
+    segments lie in the trimmed read)."""
     seq_codes = np.asarray(seq_codes, np.uint8)
     if strand:
         flag |= SAM_FSR
-    out = [name, str(flag), chr_name, str(int(ori_pos)), "0", "".join(f"{int(l)}{CIGAR_OPS[int(op)]}" for op, l in cigar),
-           "*", "0", "0"]
+    full = len(seq_codes)
+    clip_len = full if clip_len is None else int(clip_len)
+    text = clipped_cigar([(int(op) << 28) | int(l) for op, l in cigar], strand, full - clip_len)
+    out = [name, str(flag), chr_name, str(int(ori_pos)), "0", text, "*", "0", "0"]
     if strand == 0:
         out.append("".join(SEQ_FWD[c] for c in seq_codes))
     else:
         out.append("".join(SEQ_REV[c] for c in seq_codes[::-1]))
     out.append("*" if qual is None else (qual[::-1] if strand else qual))
+    out += clip_tags(clip_len, full, bc)
     out += [f"XT:A:{XT[4]}", f"{'NM' if comp_read else 'CM'}:i:0", f"X0:i:{int(c1)}"]
     if c1 <= max_top2:
         out.append(f"X1:i:{int(c2)}")
@@ -125,12 +157,14 @@ def pack_strings(items):
     return np.frombuffer(b"".join(raw), np.uint8).copy(), off
 
 
-def line_bound(max_name, max_len, max_chr, cigar_stride, md_stride, max_xa) -> int:
+def line_bound(max_name, max_len, max_chr, cigar_stride, md_stride, max_xa, trimmed=False, bc_len=0) -> int:
     """An upper bound of a line's length with its newline (hsa_sam_batch64_t.max_line): every
     number at the most digits its type has (u32: 10, u64: 20, a CIGAR length 9, n_mm 5, a
-    gap count 3), cut to the most the call takes."""
+    gap count 3), cut to the most the call takes.  max_len: the longest stored read.  trimmed:
+    reads may be trimmed (one more CIGAR op and the XC tag); bc_len: the BC tag's bytes."""
     from ._lib import HSA_SAM_MAX_LINE
     cigar = 10 * cigar_stride
+    max_name += (10 + 6 + 10 if trimmed else 0) + (6 + bc_len if bc_len else 0)
     n = (max_name + 1 + 10 + 1 + max_chr + 1 + 20 + 1 + 10 + 1 + cigar + 7 + max_len + 1 + max(max_len, 1)
          + 7 + 6 + 10 + 6 + 20 + 6 + 20 + 6 + 5 + 6 + 3 + 6 + 3 + 6 + md_stride + 1)
     if max_xa:
@@ -138,7 +172,7 @@ def line_bound(max_name, max_len, max_chr, cigar_stride, md_stride, max_xa) -> i
     return min(n, HSA_SAM_MAX_LINE)
 
 
-def device_sam(gi, dev, names, quals, chr_names, max_top2=30, flag=0, comp_read=True, on_device=False):
+def device_sam(gi, dev, names, quals, chr_names, max_top2=30, flag=0, comp_read=True, on_device=False, full_len=None, bc=None):
     """The SAM text of a batch: (text as bytes, line_off (n + 1 u64), line_stat (n u32),
     counters (8 u64)) of one hsa_sam_lines_device64 call, run a second time with
     counters[0] bytes of room when the first reports wanted > written.
@@ -149,11 +183,18 @@ def device_sam(gi, dev, names, quals, chr_names, max_top2=30, flag=0, comp_read=
     Names and qualities that are on the device already (hsa_amd.reads.load_device) are given
     as a pair of tensors instead of a list: (the bytes, the n + 1 u64 offsets of these reads; a
     sub-range's offsets are a view from its first read on).  on_device: the text and line_off stay
-    device tensors (the text's first counters[1] bytes hold)."""
+    device tensors (the text's first counters[1] bytes hold).  full_len: a device tensor of
+    the reads' stored lengths (u32 per job; jobs' len is then the trimmed length), or None;
+    bc: (a device tensor of the reads' barcodes, the bytes per read), or None.  Both default
+    to what dev holds (hsa_amd.chain's optional batch keys)."""
     import torch
     from . import chain
     from ._lib import JOB_DTYPE
     n = int(dev["n_jobs"])
+    if full_len is not None:
+        dev = dict(dev, full_len=full_len)
+    if bc is not None:
+        dev = dict(dev, bc=bc[0], bc_len=int(bc[1]))
     on_dev = isinstance(names, tuple)
     if quals is not None and on_dev != isinstance(quals, tuple):
         raise ValueError("names and qualities come both as lists or both as device tensors")
@@ -176,13 +217,17 @@ def device_sam(gi, dev, names, quals, chr_names, max_top2=30, flag=0, comp_read=
             t.update(quals=up(qb), qual_off=up(qoff))
     jobs = np.frombuffer(dev["jobs"][:n * JOB_DTYPE.itemsize].cpu().numpy().tobytes(), JOB_DTYPE) if n else np.zeros(0, JOB_DTYPE)
     lens = jobs["len"].astype(np.int64)
+    trimmed = dev.get("full_len") is not None
+    if trimmed and n:
+        lens = dev["full_len"][:n].cpu().numpy().view(np.uint32).astype(np.int64)
     max_xa = int(dev["sel"][:4 * n].view(-1, 4)[:, 3].max().item()) & 0xFFFFFFFF if n else 0
     max_chr = int(np.diff(coff.astype(np.int64)).max()) if len(chr_names) else 0
     max_line = max(1, line_bound(int(np.diff(noff.astype(np.int64)).max()) if n else 0, int(lens.max()) if n else 0, max_chr,
-                                 int(dev["cigar_stride"]), int(dev["md_stride"]), min(max_xa, 1 << 16)))
+                                 int(dev["cigar_stride"]), int(dev["md_stride"]), min(max_xa, 1 << 16), trimmed,
+                                 int(dev.get("bc_len") or 0)))
     # room: the strings as they are, a typical line's numbers and tags; a batch that needs
     # more says so in counters[0]
-    cap = int(len(nb) + (2 if quals is not None else 1) * lens.sum() + n * (160 + max_chr) + 64)
+    cap = int(len(nb) + (2 if quals is not None else 1) * lens.sum() + n * (160 + max_chr + int(dev.get("bc_len") or 0)) + 64)
     o, ctr = chain.sam_lines64(gi, dev, t, len(chr_names), max_line, cap, flag=flag, max_top2=max_top2, comp_read=comp_read)
     out = o["out"]
     written = int(ctr[1])

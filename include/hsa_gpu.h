@@ -819,6 +819,25 @@ typedef struct {
     uint64_t *d_counters;            /* >= 8 u64 */
 } hsa_sam_batch64_t;
 int hsa_sam_lines_device64(hsa_index_t *ix, const hsa_sam_batch64_t *b, void *stream);
+/* Trimmed reads and barcodes (bwa aln -q, -B; hsa_reads_device_opts leaves both arrays), for
+ * the two line writers.  d_full_len (n_jobs u32, or NULL: every read is whole): the length a
+ * read is stored with at hsa_job_t.off and in d_quals, at least hsa_job_t.len, which is then
+ * clip_len, the length the search saw.  The writers print SEQ and QUAL over the stored
+ * length (reversed over it on the reverse strand), apply bwa_correct_trimmed (bwtse.c:496-534)
+ * to the line's own CIGAR (the stored minus the searched length joins a last S op on the
+ * forward strand, a first one on the reverse strand, or becomes an S op there; the XA
+ * rows' CIGARs stay as they are), and print "\tXC:i:<hsa_job_t.len>" behind QUAL for a
+ * trimmed read.  d_bc (bc_len bytes per job, bc_len 1..HSA_SAM_MAX_BC, or NULL and 0):
+ * "\tBC:Z:<the read's bytes>" behind QUAL, before XC (:755-758).  max_line must bound the
+ * longer lines.  With `trim` NULL the calls are hsa_sam_lines_device64 and
+ * hsa_splice_lines_device, byte for byte. */
+#define HSA_SAM_MAX_BC 63u
+typedef struct {
+    const uint32_t *d_full_len;
+    const uint8_t *d_bc;
+    uint32_t bc_len;
+} hsa_sam_trim_t;
+int hsa_sam_lines_device64_trim(hsa_index_t *ix, const hsa_sam_batch64_t *b, const hsa_sam_trim_t *trim, void *stream);
 /* Probes, as hsa_choose_timing / hsa_choose_launch_times: the HSA_SAM_LAUNCHES times in ms of
  * the handle's last timed call: k_sam_len (with the counters' memsets), the scan,
  * k_sam_write. */
@@ -900,6 +919,8 @@ typedef struct {
     uint64_t *d_counters;            /* >= 8 u64 */
 } hsa_splice_lines_batch_t;
 int hsa_splice_lines_device(hsa_index_t *ix, const hsa_splice_lines_batch_t *b, void *stream);
+/* ... with trimmed reads and barcodes (hsa_sam_trim_t above; the segments lie in hsa_job_t.len) */
+int hsa_splice_lines_device_trim(hsa_index_t *ix, const hsa_splice_lines_batch_t *b, const hsa_sam_trim_t *trim, void *stream);
 /* The lines of two writers over the same reads (hsa_sam_lines_device64's and
  * hsa_splice_lines_device's: a read has a line from at most one of them) as one text in read
  * order: d_line_off[j] is the sum of the two inputs' offsets, and read j's bytes are writer
@@ -964,12 +985,39 @@ int hsa_sam_merge_device(hsa_index_t *ix, const hsa_sam_merge_batch_t *b, void *
  * longest loaded read, [14] the longest kept read, [15] the threshold (as int64).  wanted >
  * written: run again with more room; no byte at or past a capacity is touched.
  *
- * Not built: quality trimming (-q), barcodes (-B), the Casava filter (-Y), Illumina-1.3
- * qualities (-I), BAM input (-b): trim_qual != 0 or one of those bits of `mode` (gap_opt_t.mode
- * as bwa_aln sets it) is HSA_E_ARG, as are null pointers and n_in >= 2^32 - 256. */
+ * hsa_reads_device takes none of the reader's options: trim_qual != 0, a barcode length, the
+ * Casava, Illumina-1.3 or BAM bits of `mode` (gap_opt_t.mode as bwa_aln sets it) are HSA_E_ARG
+ * there, as are null pointers and n_in >= 2^32 - 256.
+ *
+ * hsa_reads_device_opts is the same call with bwa_read_seq's options, applied per canonical
+ * record in its order (bwaseqio.c:176-211):
+ *   -Y  (mode & 0x08) the record is skipped when its comment (the header line behind the
+ *       name's white space) is not empty, holds a ':' before any NUL, and the byte after the
+ *       first ':' is 'Y';
+ *   -I  (mode & 0x200) 31 comes off every quality byte; the bytes are validated as given
+ *       (33..127) and stored shifted;
+ *   -B n (mode >> 24, at most 63) a record of n bases or fewer is skipped; the first n bases
+ *       go to d_bc (n bytes per job: lower case where the shifted quality - 33 is under 13,
+ *       else upper case) and sequence and quality lose them;
+ *   -q  (trim_qual >= 1, at most 32 674: the walk's sum then fits 32 bits for a read of
+ *       HSA_RD_MAX_LEN) bwa_trim_read (:92-103): hsa_job_t.len, the row's length, max_diff,
+ *       seed_len, the codes above 3, the poly test, the threshold and [13] / [14] are of the
+ *       trimmed read.  The stored read stays whole: hsa_job_t.off, d_qual_off and the
+ *       wanted / written byte counts advance by the length before trimming, which d_full_len
+ *       (one u32 per job) holds.  A read of 35 bases or fewer is never trimmed.
+ * A skipped record gets a row of status HSA_RD_FILTERED (length and count 0) and no job, and does not count towards
+ * max_records nor [1].  With -Y or -B the call looks at no more than rec_cap records
+ * (0: max_records), the rows d_rec holds, and loads up to the max_records-th record it does not
+ * skip; [0] counts the skipped ones too, [10] and [11] speak of records as the input holds them.
+ * d_opt_counters (>= HSA_RD_OPT_COUNTERS u64, or NULL): [0] records loaded, the skipped ones
+ * included (the rows written), [1] records skipped, [2] bases trimmed and [3] bases in all, over
+ * the loaded records not skipped (the reference's "% bases are trimmed").  BAM input (mode &
+ * 0x1e0) is not built: HSA_E_ARG. */
 #define HSA_RD_SEARCHED 0u
 #define HSA_RD_NDROP    1u    /* more codes above 3 than the threshold */
 #define HSA_RD_POLYAT   2u    /* the first 15 codes all A or all T */
+#define HSA_RD_FILTERED 3u    /* skipped by the reader: the Casava filter, or not longer than the barcode */
+#define HSA_RD_OPT_COUNTERS 4
 #define HSA_RD_ROW_WORDS 4
 #define HSA_RD_MAX_LEN  65535u
 #define HSA_RD_TILE     4096u /* bytes of the input per block of the newline passes */
@@ -982,18 +1030,25 @@ typedef struct {
     uint32_t len_floor;              /* the longest read of the batch's other chunks, or 0 */
     int32_t seed_len;                /* opt->seed_len */
     int32_t regime;                  /* written to every job */
-    int32_t trim_qual; uint32_t mode; /* must select nothing of "Not built" */
+    int32_t trim_qual; uint32_t mode; /* opt->trim_qual, opt->mode: both 0 for hsa_reads_device (its search bits aside) */
     hsa_job_t *d_jobs; uint64_t job_cap;
     uint8_t *d_codes; uint64_t code_cap;
     uint8_t *d_names; uint64_t name_cap; uint64_t *d_name_off;
     uint8_t *d_quals; uint64_t qual_cap; uint64_t *d_qual_off;
     uint32_t *d_rec;
     uint64_t *d_counters;            /* >= 16 u64 */
+    /* the reader's options; 0 / NULL: none */
+    uint32_t *d_full_len;            /* job_cap u32: a read's length before trimming (needed with trim_qual >= 1) */
+    uint8_t *d_bc;                   /* job_cap * (mode >> 24) bytes: the barcodes (needed with a barcode) */
+    uint32_t rec_cap;                /* the rows of d_rec when -Y or -B is set; 0: max_records */
+    uint64_t *d_opt_counters;        /* >= HSA_RD_OPT_COUNTERS u64, or NULL */
 } hsa_reads_batch_t;
 int hsa_reads_device(hsa_index_t *ix, const hsa_reads_batch_t *b, void *stream);
+int hsa_reads_device_opts(hsa_index_t *ix, const hsa_reads_batch_t *b, void *stream);
 /* Probes, as hsa_sam_timing / hsa_sam_launch_times: the HSA_RD_LAUNCHES times in ms of the
  * handle's last timed call: k_rd_count (with the memsets), the tile scan, k_rd_lines,
- * k_rd_record, k_rd_max with k_rd_keep, the record scan, k_rd_rows, k_rd_bytes. */
+ * k_rd_record, k_rd_max with k_rd_keep (and, with -Y or -B, the scan of the kept records and
+ * k_rd_limit before them), the record scan, k_rd_rows, k_rd_bytes. */
 #define HSA_RD_LAUNCHES 8
 void hsa_reads_timing(int on);
 int hsa_reads_launch_times(hsa_index_t *ix, float *ms);
