@@ -41,6 +41,7 @@ EXPORTS = [  # every symbol include/hsa_gpu.h and include/hsa_bwtaln.h declare
     "hsa_sam_launch_times", "hsa_index_levels", "hsa_reads_device", "hsa_reads_timing",
     "hsa_reads_launch_times", "hsa_reads_device_opts", "hsa_sam_lines_device64_trim", "hsa_splice_lines_device_trim", "hsa_fasta_scratch_bytes", "hsa_fasta_device", "hsa_bwt_files_scratch_bytes",
     "hsa_bwt_files_device", "hsa_fasta_timing", "hsa_fasta_launch_times", "hsa_bwt_files_launch_times",
+    "hsa_inflate_bgzf_device",
 ]
 SP_RES_WORDS = 20  # hsa_splice_match_batch's per-read answer (include/hsa_gpu.h)
 ALN64_WORDS = 14   # hsa_aln64_t (include/hsa_gpu.h)
@@ -78,6 +79,12 @@ FA_COUNTERS = ("seen", "kept", "rec_written", "blocks", "blk_written", "characte
 FA_PAD_WORDS = 8
 FA_LAUNCHES = ("marks", "marks_scan", "spans", "span_scans", "count", "count_scan", "pack", "reverse")
 BF_LAUNCHES = ("blocks", "scan", "samples")
+# hsa_inflate_bgzf_device: per-block status, the counters, a row of the block table (hsa_bgzf_block_t)
+(HSA_INF_OK, HSA_INF_E_INPUT, HSA_INF_E_BTYPE, HSA_INF_E_STORED, HSA_INF_E_CODES, HSA_INF_E_SYMBOL, HSA_INF_E_DIST,
+ HSA_INF_E_OUTPUT, HSA_INF_E_SIZE, HSA_INF_E_CRC, HSA_INF_E_TRAIL, HSA_INF_E_ROW) = range(12)
+INF_COUNTERS = ("done", "refused", "bytes")
+BGZF_BLOCK_DTYPE = np.dtype([("in_off", "<u8"), ("in_len", "<u4"), ("isize", "<u4"), ("out_off", "<u8"), ("crc", "<u4"),
+                             ("reserved", "<u4")])
 
 
 class HsaError(RuntimeError):
@@ -260,6 +267,21 @@ class FastaBatch(C.Structure):
                 ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_uint64)]
 
 
+class InflateBatch(C.Structure):
+    """hsa_inflate_batch_t (include/hsa_gpu.h): the bytes of a BGZF file and its block table
+    in; the text, a status per block and the counters out.  All device pointers."""
+    _fields_ = [("d_in", C.c_void_p), ("n_in", C.c_uint64), ("d_blocks", C.c_void_p), ("n_blocks", C.c_uint64),
+                ("d_out", C.c_void_p), ("out_cap", C.c_uint64), ("d_status", C.c_void_p), ("d_counters", C.c_void_p)]
+
+
+def inflate_bgzf_device(batch: "InflateBatch", device: int = 0, stream=None):
+    """hsa_inflate_bgzf_device: the BGZF blocks of batch.d_blocks, one wavefront each, into
+    their slices of batch.d_out; queued on `stream` (an int handle; None: the null stream)."""
+    if not hasattr(lib(), "hsa_inflate_bgzf_device"):
+        raise HsaError("this libhsa_gpu.so has no hsa_inflate_bgzf_device: rebuild it")
+    check(lib().hsa_inflate_bgzf_device(int(device), C.byref(batch), stream))
+
+
 def log_n_table() -> np.ndarray:
     """g_log_n (bwtse.c:838-842): (int)(4.343 * log(i) + 0.5) for i = 1..255, [0] = 0."""
     import math
@@ -440,6 +462,8 @@ def lib():
         L.hsa_fasta_timing.restype = None
         L.hsa_fasta_launch_times.argtypes = [f32]
         L.hsa_bwt_files_launch_times.argtypes = [f32]
+    if hasattr(L, "hsa_inflate_bgzf_device"):       # (older A/B builds lack the BGZF inflater)
+        L.hsa_inflate_bgzf_device.argtypes = [C.c_int, C.POINTER(InflateBatch), vp]
     if hasattr(L, "hsa_extend_batch"):
         L.hsa_extend_batch.argtypes = [vp, C.POINTER(Regime), C.c_int, vp, C.c_int, u8, i32, C.c_size_t, i32, i32,
                                        u32]

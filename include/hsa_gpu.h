@@ -31,6 +31,9 @@
  *   hsa_reads_device   -- bwa_read_seq over kseq_read (bwaseqio.c:161-231, kseq.h:155-193) and the
  *                         read filter of bwa_cal_sa_reg_gap (bwtaln.c:313-332) for FASTQ bytes in
  *                         device memory.
+ *   hsa_inflate_bgzf_device -- gzread (zlib's inflate with the gzip trailer's CRC32 check) for
+ *                         the members of a BGZF file whose bytes sit in device memory: the
+ *                         step in front of hsa_reads_device and hsa_fasta_device.
  *   hsa_extend_batch   -- bwt_extend_backward / bwt_extend_foreward (bwtgap.c:640-663,
  *                         bwt_backtracing_search :346-511): the splice path's seed
  *                         extensions.
@@ -1140,6 +1143,59 @@ int hsa_bwt_files_device(int device, uint64_t T, const uint32_t *d_bwt_lsb, uint
 void hsa_fasta_timing(int on);
 int hsa_fasta_launch_times(float *ms);
 int hsa_bwt_files_launch_times(float *ms);
+
+/* ---- BGZF blocks to text ----
+ * What gzread does for the reference's readers (bwaseqio.c:38, HSP.c:212) when the file is
+ * BGZF, the blocked gzip `bgzip` writes: a series of independent gzip members of at most
+ * 64 KB, each with its compressed size in the header and CRC32 and ISIZE in the trailer.
+ * The caller walks the members on the host (hsa_amd/bgzf.py: scan) and passes the file's
+ * bytes in device memory with one row per member; one wavefront inflates one member into
+ * its own slice of d_out: all of DEFLATE (RFC 1951: stored, fixed and dynamic blocks, any
+ * number per member), the CRC32 of the bytes computed on the device.
+ *
+ * d_status[i] is HSA_INF_OK only if the stream ended on a final block at the payload's last
+ * byte, exactly isize bytes were written and their CRC32 is the row's; any other value names
+ * the reason, and the slice of such a block is unspecified (the caller inflates it again on
+ * the host, which decides whether the file is corrupt).  Every read is checked against the
+ * payload's end and every write and back-reference against the block's slice before it is
+ * made: a corrupt file ends as a status, and no byte outside [in_off, in_off + in_len) of
+ * d_in and [out_off, out_off + isize) of d_out is touched for a block.  A row that lies
+ * outside d_in or d_out is HSA_INF_E_ROW.  Rows' slices must not overlap.
+ *
+ * d_counters (HSA_INF_COUNTERS u64, added to: the caller zeroes them): [0] blocks with
+ * status OK, [1] blocks refused, [2] bytes written by the OK blocks.  Takes a device
+ * number, as hsa_fasta_device does: the FASTA reader calls it before any index exists.
+ * Launches on `stream` (NULL: the null stream), does not synchronise, needs no scratch.
+ * General gzip (one serial stream) is not built: it stays on the host. */
+#define HSA_INF_OK        0u
+#define HSA_INF_E_INPUT   1u   /* the payload ended inside the stream */
+#define HSA_INF_E_BTYPE   2u   /* block type 3 */
+#define HSA_INF_E_STORED  3u   /* a stored block's LEN is not ~NLEN */
+#define HSA_INF_E_CODES   4u   /* an over-subscribed or unusable code-length set */
+#define HSA_INF_E_SYMBOL  5u   /* a code no symbol has, or length symbol 286/287, distance symbol 30/31 */
+#define HSA_INF_E_DIST    6u   /* a distance that reaches before the block's start */
+#define HSA_INF_E_OUTPUT  7u   /* output past ISIZE */
+#define HSA_INF_E_SIZE    8u   /* the stream ended with fewer than ISIZE bytes */
+#define HSA_INF_E_CRC     9u   /* the bytes' CRC32 is not the trailer's */
+#define HSA_INF_E_TRAIL   10u  /* payload bytes behind the final block */
+#define HSA_INF_E_ROW     11u  /* the row's payload or slice lies outside the buffers */
+#define HSA_INF_COUNTERS  3
+typedef struct {
+    uint64_t in_off;                 /* the deflate payload in d_in */
+    uint32_t in_len;
+    uint32_t isize;                  /* the trailer's ISIZE */
+    uint64_t out_off;                /* the block's slice in d_out */
+    uint32_t crc;                    /* the trailer's CRC32 */
+    uint32_t reserved;
+} hsa_bgzf_block_t;
+typedef struct {
+    const uint8_t *d_in; uint64_t n_in;
+    const hsa_bgzf_block_t *d_blocks; uint64_t n_blocks;   /* under 2^31 */
+    uint8_t *d_out; uint64_t out_cap;
+    uint32_t *d_status;              /* n_blocks */
+    uint64_t *d_counters;            /* HSA_INF_COUNTERS */
+} hsa_inflate_batch_t;
+int hsa_inflate_bgzf_device(int device, const hsa_inflate_batch_t *b, void *stream);
 
 #ifdef __cplusplus
 }
