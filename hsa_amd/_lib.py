@@ -41,7 +41,7 @@ EXPORTS = [  # every symbol include/hsa_gpu.h and include/hsa_bwtaln.h declare
     "hsa_sam_launch_times", "hsa_index_levels", "hsa_reads_device", "hsa_reads_timing",
     "hsa_reads_launch_times", "hsa_reads_device_opts", "hsa_sam_lines_device64_trim", "hsa_splice_lines_device_trim", "hsa_fasta_scratch_bytes", "hsa_fasta_device", "hsa_bwt_files_scratch_bytes",
     "hsa_bwt_files_device", "hsa_fasta_timing", "hsa_fasta_launch_times", "hsa_bwt_files_launch_times",
-    "hsa_inflate_bgzf_device",
+    "hsa_inflate_bgzf_device", "hsa_bam_reads_device", "hsa_bam_timing", "hsa_bam_launch_times",
 ]
 SP_RES_WORDS = 20  # hsa_splice_match_batch's per-read answer (include/hsa_gpu.h)
 ALN64_WORDS = 14   # hsa_aln64_t (include/hsa_gpu.h)
@@ -71,6 +71,11 @@ HSA_RD_TILE = 4096
 RD_COUNTERS = ("seen", "loaded", "jobs_wanted", "jobs_written", "code_wanted", "code_written", "name_wanted",
                "name_written", "qual_wanted", "qual_written", "consumed", "bad_record", "bad_offset", "max_loaded",
                "max_kept", "threshold")
+# hsa_bam_reads_device: why the load ended (d_bam_counters[0]), the BAM counters, the launches
+(HSA_BAM_END_MAX, HSA_BAM_END_INPUT, HSA_BAM_END_INCOMPLETE, HSA_BAM_END_ANCHOR, HSA_BAM_END_HOST,
+ HSA_BAM_END_MALFORMED) = range(6)
+BAM_COUNTERS = ("reason", "segments_verified", "chain_records", "chain_end")
+BAM_LAUNCHES = ("walk", "segment_scan", "starts", "record", "max_keep", "record_scan", "rows", "bytes")
 # hsa_fasta_device: words per record row, the counters, the zero words behind a text
 FA_REC_WORDS = 4
 FA_COUNTERS = ("seen", "kept", "rec_written", "blocks", "blk_written", "characters", "total", "T", "rev_T",
@@ -254,6 +259,19 @@ class ReadsBatch(C.Structure):
                 ("name_cap", C.c_uint64), ("d_name_off", C.c_void_p), ("d_quals", C.c_void_p), ("qual_cap", C.c_uint64),
                 ("d_qual_off", C.c_void_p), ("d_rec", C.c_void_p), ("d_counters", C.c_void_p),
                 ("d_full_len", C.c_void_p), ("d_bc", C.c_void_p), ("rec_cap", C.c_uint32), ("d_opt_counters", C.c_void_p)]
+
+
+class BamBatch(C.Structure):
+    """hsa_bam_batch_t (include/hsa_gpu.h): the inflated bytes of a BAM file from a record start
+    on and the anchors in; ReadsBatch's outputs and the BAM counters out, all device pointers."""
+    _fields_ = [("d_in", C.c_void_p), ("n_in", C.c_uint64), ("at_eof", C.c_int32), ("max_records", C.c_uint32),
+                ("which", C.c_uint32), ("trim_qual", C.c_int32), ("max_diff", C.c_int32), ("d_maxdiff", C.c_void_p),
+                ("n_maxdiff", C.c_uint32), ("len_floor", C.c_uint32), ("seed_len", C.c_int32), ("regime", C.c_int32),
+                ("d_anchor", C.c_void_p), ("n_anchor", C.c_uint32), ("d_jobs", C.c_void_p), ("job_cap", C.c_uint64),
+                ("d_codes", C.c_void_p), ("code_cap", C.c_uint64), ("d_names", C.c_void_p), ("name_cap", C.c_uint64),
+                ("d_name_off", C.c_void_p), ("d_quals", C.c_void_p), ("qual_cap", C.c_uint64), ("d_qual_off", C.c_void_p),
+                ("d_full_len", C.c_void_p), ("d_rec", C.c_void_p), ("rec_cap", C.c_uint32), ("d_counters", C.c_void_p),
+                ("d_opt_counters", C.c_void_p), ("d_bam_counters", C.c_void_p)]
 
 
 class FastaBatch(C.Structure):
@@ -462,6 +480,14 @@ def lib():
         L.hsa_fasta_timing.restype = None
         L.hsa_fasta_launch_times.argtypes = [f32]
         L.hsa_bwt_files_launch_times.argtypes = [f32]
+    if hasattr(L, "hsa_bam_reads_device"):          # (older A/B builds lack the BAM loader)
+        L.hsa_bam_reads_device.argtypes = [vp, C.POINTER(BamBatch), vp]
+        L.hsa_bam_timing.argtypes = [C.c_int]
+        L.hsa_bam_timing.restype = None
+        if hasattr(L, "hsa_bam_walk_mode"):         # (the probe's knob: not in the public header)
+            L.hsa_bam_walk_mode.argtypes = [C.c_int]
+            L.hsa_bam_walk_mode.restype = None
+        L.hsa_bam_launch_times.argtypes = [vp, C.POINTER(C.c_float)]
     if hasattr(L, "hsa_inflate_bgzf_device"):       # (older A/B builds lack the BGZF inflater)
         L.hsa_inflate_bgzf_device.argtypes = [C.c_int, C.POINTER(InflateBatch), vp]
     if hasattr(L, "hsa_extend_batch"):
@@ -874,6 +900,20 @@ class GpuIndex:
         if not hasattr(lib(), "hsa_reads_device"):
             raise HsaError("this libhsa_gpu.so has no hsa_reads_device: rebuild it")
         check(lib().hsa_reads_device(getattr(self, "h", None), C.byref(batch), stream))
+
+    def bam_reads_device(self, batch: "BamBatch", stream=None):
+        """hsa_bam_reads_device: the inflated bytes of a BAM file on the device to the search
+        batch reads_device_opts leaves; queued on `stream` (None: the index's)."""
+        if not hasattr(lib(), "hsa_bam_reads_device"):
+            raise HsaError("this libhsa_gpu.so has no hsa_bam_reads_device: rebuild it")
+        check(lib().hsa_bam_reads_device(getattr(self, "h", None), C.byref(batch), stream))
+
+    def bam_launch_times(self):
+        """hsa_bam_launch_times: ms per launch (BAM_LAUNCHES) of this handle's last
+        bam_reads_device call made under hsa_bam_timing(1)."""
+        ms = (C.c_float * len(BAM_LAUNCHES))()
+        check(lib().hsa_bam_launch_times(self.h, ms))
+        return dict(zip(BAM_LAUNCHES, (float(v) for v in ms)))
 
     def reads_device_opts(self, batch: "ReadsBatch", stream=None):
         """hsa_reads_device_opts: reads_device with the reader's options of batch.trim_qual and

@@ -58,7 +58,26 @@ written to --unaligned, and is counted as `filtered`; `trimmed_bases` of `total_
 the reference reports as "% bases are trimmed".  --unaligned writes a read's record as it was
 given, barcode included.
 
-Not built: BAM input (-b, -0, -1, -2), colour space (-c): refused.  -t is accepted and
+BAM input (-b, with -0, -1, -2 to select the records; hsa_amd.bam states the rule): align_fastq
+with the BAM bit of opts["mode"] takes a path or the file's bytes, opens the text through
+bam.open_text (BGZF inflated on the device, the text kept resident), reads the header on the
+host and loads every batch through hsa_bam_reads_device (_load_batch_bam): windows of the
+resident text, or of the host text uploaded when the inflater needed several groups, with the
+BGZF members' first bytes inside the window as anchors.  A call that ends on an anchor that is
+not on the record chain keeps what it loaded and the rest of the batch comes from the
+single-anchor walk; records the device does not take (an empty name, a read past the max_diff
+table) go through bam.parse_host.  Everything after the load is the code above.  -B, -I and
+-Y have no effect on BAM input (bwaseqio.c:172) and are ignored; -0, -1, -2 without -b have
+none either (the file is then opened as FASTQ, bwtaln.c:441).  --unaligned writes a BAM read
+as a FASTQ record in the read's own orientation.  The statistics gain inflate_* (the
+inflater's), bam_segments (the segments the calls were given: one more key than the loader's
+issue lists, the figure bam_segments_verified is read against) and bam_segments_verified,
+bam_serial_records (records found by a
+single-anchor walk) and bam_truncated: a truncated or inconsistent record ends the input
+there, the reads before it are aligned, and main returns 1.  Without the BAM bit nothing
+changes, the keys of the statistics included.
+
+Not built: colour space (-c): refused.  -t is accepted and
 ignored.  A read the choice counts as a zero-draw read (probability 2^-48 per read) stops the
 run with an error."""
 from __future__ import annotations
@@ -69,7 +88,7 @@ import sys
 
 import numpy as np
 
-from . import chain, index_io, reads, sam
+from . import bam, chain, index_io, reads, sam
 from ._lib import (ALN64_WORDS, DRAND48_SEED0, HSA_RD_NDROP, HSA_RD_POLYAT, HSA_RD_SEARCHED, HSA_RF_MAX_LEN, HSA_SP_MAX_STACKS,
                    JOB_DTYPE, SP_RES_WORDS, GapOpt, GpuIndex, regime_of)
 
@@ -78,6 +97,8 @@ BATCH_READS = 0x186A0            # bwtaln.c:477
 MODE_GAPE, MODE_COMPREAD, MODE_LOGGAP, MODE_NONSTOP = 0x01, 0x02, 0x04, 0x10
 MODE_CFY, MODE_IL13 = reads.MODE_CFY, reads.MODE_IL13
 MODE_READER = MODE_CFY | MODE_IL13 | 0xFF000000          # what bwa_read_seq takes of gap_opt_t.mode (the barcode length on top)
+MODE_BAM, MODE_BAM_ALL = bam.MODE_BAM, bam.MODE_BAM_ALL   # -b; with -0, -1, -2 (bwtaln.h:127-130)
+_BAM_BITS = {"-b": bam.MODE_BAM, "-0": bam.MODE_BAM_SE, "-1": bam.MODE_BAM_READ1, "-2": bam.MODE_BAM_READ2}
 SEED_NONE = reads.SEED_NONE
 TABLE_LEN = HSA_RF_MAX_LEN + 1   # reads past it go through the host parser (and are not refined)
 ONES = 0xFFFFFFFFFFFFFFFF
@@ -109,14 +130,16 @@ def _atof(s: str) -> float:
     return float(m.group(0)) if m else 0.0
 
 
-def parse_options(args, reader_options=False):
+def parse_options(args, reader_options=False, bam_options=False):
     """bwa_aln's option switch (bwtaln.c:539-575) over `args`: (the option dict, the
     positional arguments, dict(header, unaligned, out)).  Options of what is not built raise
     ValueError.  reader_options: take the reader's options as the switch sets them (:558,
     :566-568): -q INT (trim_qual), -B INT (mode |= n << 24), -I (MODE_IL13), -Y (MODE_CFY); a
     barcode over BWA_MAX_BCLEN (the reference then reads nothing) and a trim_qual over
     reads.MAX_TRIM_QUAL are ValueError.  Without it they are refused, as before the reader
-    had them; the command line (main) sets it."""
+    had them; the command line (main) sets it.  bam_options: take -b, -0, -1, -2 as the switch
+    sets them (:562-565: MODE_BAM, MODE_BAM_SE, MODE_BAM_READ1, MODE_BAM_READ2); without it they
+    are refused, whatever reader_options says."""
     import getopt
     o = default_opts()
     extra = dict(header=False, unaligned=None, out=None)
@@ -150,6 +173,8 @@ def parse_options(args, reader_options=False):
             o["mode"] |= MODE_IL13
         elif k == "-Y" and reader_options:
             o["mode"] |= MODE_CFY
+        elif k in _BAM_BITS and bam_options:
+            o["mode"] |= _BAM_BITS[k]
         elif k == "-f":
             extra["out"] = v
         elif k == "--header":
@@ -159,7 +184,7 @@ def parse_options(args, reader_options=False):
         elif k == "--splice":
             extra["splice"] = True                          # (the key is there only when the option is)
         else:
-            raise ValueError(f"option {k} is not built" + (" (BAM input, colour space)" if reader_options else
+            raise ValueError(f"option {k} is not built" + (" (colour space)" if bam_options else " (BAM input, colour space)" if reader_options else
                                                            " (barcodes, Casava filter, Illumina-1.3 qualities, BAM, colour space)"))
     if opte > 0:
         o["max_gape"] = opte
@@ -317,6 +342,65 @@ def _load_batch(gi, data, pos, opt, d_table, batch_reads, window):
     return segs, pos, window
 
 
+def _load_batch_bam(gi, src, pos, opt, d_table, batch_reads, window, stats):
+    """_load_batch for the BAM text of src (dict: text, d_text or None, cand: the anchor
+    candidates as offsets in the text, which): records from the record start `pos` on, through
+    hsa_bam_reads_device (bam.load_device) on a window of the resident text, or of the host
+    text uploaded when the inflater left none.  Anchors: the window's start and the candidates
+    inside the window behind it.  A call that ends on an anchor that is not on the chain keeps
+    what it loaded (exact up to there), and the rest of the batch is loaded with the
+    single-anchor walk.  A record the device does not take goes through bam.parse_host, and
+    the loader goes on behind it.  A truncated or inconsistent record ends the input:
+    stats["bam_truncated"]."""
+    from ._lib import HSA_BAM_END_ANCHOR, HSA_BAM_END_MALFORMED
+    text, cand, which = src["text"], src["cand"], src["which"]
+    segs, have, host_n, serial = [], 0, 1, False
+    while have < batch_reads and pos < len(text):
+        w = min(len(text) - pos, window)
+        at_eof = pos + w == len(text)
+        d_in, first = (src["d_text"], pos) if src["d_text"] is not None else (reads.upload(text[pos:pos + w]), 0)
+        inside = cand[(cand > pos) & (cand < pos + w)] - np.uint64(pos) if not serial else cand[:0]
+        anchors = np.concatenate([np.zeros(1, np.uint64), inside.astype(np.uint64)])
+        room = batch_reads - have
+
+        def call(floor=0, d_in=d_in, first=first, w=w, at_eof=at_eof, room=room, anchors=anchors):
+            return bam.load_device(gi, d_in, w, at_eof, room, opt["max_diff"], opt["seed_len"], anchors=anchors, which=which,
+                                   maxdiff=d_table, trim_qual=opt["trim_qual"], first=first, len_floor=floor)
+        t = call()
+        c, got, reason = t["ctr"], t["n_loaded"], t["bctr"]["reason"]
+        stats["bam_segments"] += len(anchors)
+        stats["bam_segments_verified"] += t["bctr"]["segments_verified"]
+        if len(anchors) == 1:
+            stats["bam_serial_records"] += t["n_rows"]
+        if t["n_rows"]:
+            segs.append(dict(kind="dev", t=t, span=(pos, w, at_eof, room), reload=call,
+                             host=lambda t, pos=pos: bam.parse_host(text[pos:pos + t["ctr"]["consumed"]], None, which=which,
+                                                                    trim_qual=opt["trim_qual"])))
+            have += got
+        pos += c["consumed"]
+        if reason == HSA_BAM_END_ANCHOR:
+            serial = True
+        elif reason == HSA_BAM_END_MALFORMED:
+            stats["bam_truncated"] = 1
+            return segs, len(text), window
+        elif c["bad_record"] != ONES:
+            host_n = 1 if got else min(2 * host_n, 1 << 20)
+            p = bam.parse_host(text, min(host_n, batch_reads - have), start=pos, which=which, trim_qual=opt["trim_qual"])
+            if p["names"] or p["filtered"]:
+                segs.append(dict(kind="host", p=p))
+                have += len(p["names"])
+            pos = p["consumed"]
+            if p["end"] == -2:
+                stats["bam_truncated"] = 1
+                return segs, len(text), window
+        elif t["n_rows"] == 0 and c["consumed"] == 0:
+            if at_eof:
+                pos = len(text)
+            else:
+                window *= 2                  # a record longer than the window
+    return segs, pos, window
+
+
 def _merge(gi, data, segs, opt, d_table):
     """One device batch of the segments: the tensors of load_device's keys, the per-record
     rows on the host (job indices of the batch; the records the reader skipped have none),
@@ -340,10 +424,13 @@ def _merge(gi, data, segs, opt, d_table):
                     ((rec[:, 0] == HSA_RD_NDROP) & (rec[:, 2].astype(np.int64) <= thr)).any():
                 pos, w, at_eof, room = s["span"]           # the chunk alone set a narrower threshold
                 if max_all < TABLE_LEN:
-                    t = reads.load_device(gi, reads.upload(data[pos:pos + w]), w, at_eof, room, opt["max_diff"], opt["seed_len"],
+                    t = s["reload"](max_all) if "reload" in s else \
+                        reads.load_device(gi, reads.upload(data[pos:pos + w]), w, at_eof, room, opt["max_diff"], opt["seed_len"],
                                           maxdiff=d_table, len_floor=max_all, **rd)
                     assert t["n_rows"] == n_rec and t["ctr"]["threshold"] == (thr & ONES)
                     rec = t["rec"][:4 * n_rec].cpu().numpy().view(np.uint32).reshape(-1, 4).copy()
+                elif "host" in s:
+                    s = dict(kind="host", p=s["host"](t))
                 else:
                     s = dict(kind="host", p=reads.parse_host(data[pos:pos + t["ctr"]["consumed"]], t["n_loaded"], **rd))
         if s["kind"] == "dev":
@@ -581,7 +668,8 @@ def _read_input(data_or_path) -> bytes:
 
 def align_fastq(gi, chr_names, data_or_path, opts, out, batch_reads=BATCH_READS, rng_state=HSA_DRAND48_SEED0, unaligned=None,
                 splice=False):
-    """FASTQ (bytes, or a path; gzip is read through Python's gzip) to SAM text written to
+    """FASTQ (bytes, or a path; gzip is read through Python's gzip), or with the BAM bit of
+    opts["mode"] a BAM file (bytes or a path; the module docstring), to SAM text written to
     `out` (a binary file object), as the module docstring states it.  opts: an option dict
     (default_opts / parse_options), not modified.  unaligned: a binary file object for the
     reads without a line.  splice: send the reads without a main-search hit through the splice
@@ -589,11 +677,21 @@ def align_fastq(gi, chr_names, data_or_path, opts, out, batch_reads=BATCH_READS,
     after the last read, statistics)."""
     import collections
     import torch
-    data = _read_input(data_or_path)
     opt = dict(opts)
     opt.setdefault("trim_qual", 0)
-    if opt["mode"] & ~(MODE_GAPE | MODE_COMPREAD | MODE_LOGGAP | MODE_NONSTOP | MODE_READER):
-        raise ValueError("BAM input is not built")
+    is_bam = bool(opt["mode"] & MODE_BAM)
+    if opt["mode"] & ~(MODE_GAPE | MODE_COMPREAD | MODE_LOGGAP | MODE_NONSTOP | MODE_READER | MODE_BAM_ALL):
+        raise ValueError("a mode bit that is not built")
+    src = None
+    if is_bam:
+        # -B, -I and -Y have no effect on BAM input (bwaseqio.c:172): accepted and ignored
+        src = dict(which=bam.which_of(opt["mode"]))
+        opt["mode"] &= ~(MODE_BAM_ALL | MODE_READER)
+        src["text"], src["d_text"], src["cand"], inflate = bam.open_text(gi, data_or_path)
+        data = src["text"]
+    else:
+        opt["mode"] &= ~MODE_BAM_ALL                         # -0, -1, -2 without -b: the file is opened as FASTQ (bwtaln.c:441)
+        data = _read_input(data_or_path)
     if (opt["mode"] >> 24) > reads.BWA_MAX_BCLEN or opt["trim_qual"] > reads.MAX_TRIM_QUAL:
         raise ValueError(f"a barcode of at most {reads.BWA_MAX_BCLEN} bases, trim_qual at most {reads.MAX_TRIM_QUAL}")
     rd = dict(mode=opt["mode"] & MODE_READER, trim_qual=opt["trim_qual"])
@@ -612,9 +710,16 @@ def align_fastq(gi, chr_names, data_or_path, opts, out, batch_reads=BATCH_READS,
                      spliced_refused=0)
         stats["refused_names"] = []
     pos, state, window = 0, int(rng_state), max(4 << 20, 1024 * int(batch_reads))
+    if is_bam:
+        stats.update({"inflate_" + k: v for k, v in inflate.items()})
+        stats.update(bam_segments=0, bam_segments_verified=0, bam_serial_records=0, bam_truncated=0)
+        pos, window = bam.read_header(data)[0], max(1 << 20, 256 * int(batch_reads))
     while pos < len(data):
         start = pos
-        segs, pos, window = _load_batch(gi, data, pos, opt, d_table, int(batch_reads), window)
+        if is_bam:
+            segs, pos, window = _load_batch_bam(gi, src, pos, opt, d_table, int(batch_reads), window, stats)
+        else:
+            segs, pos, window = _load_batch(gi, data, pos, opt, d_table, int(batch_reads), window)
         if not segs:
             break                                           # bwa_read_seq returned no read: bwtaln.c:477 ends
         b = _merge(gi, data, segs, opt, d_table)
@@ -628,7 +733,8 @@ def align_fastq(gi, chr_names, data_or_path, opts, out, batch_reads=BATCH_READS,
         stats["host_records"] += sum(len(s["p"]["names"]) for s in segs if s["kind"] == "host")
         state, has_line = _run_batch(gi, chr_names, b, opt, out, state, stats, splice=splice)
         if unaligned is not None:
-            p = reads.parse_host(data[start:pos], len(rec), **rd)
+            p = bam.parse_host(data[start:pos], len(rec), which=src["which"], trim_qual=opt["trim_qual"]) if is_bam else \
+                reads.parse_host(data[start:pos], len(rec), **rd)
             assert len(p["names"]) == len(rec)
             for r in range(len(rec)):
                 if rec[r, 0] == HSA_RD_SEARCHED and has_line[int(rec[r, 3])]:
@@ -651,12 +757,12 @@ def sam_header(prefix: str) -> bytes:
 def main(argv=None) -> int:
     argv = sys.argv[1:] if argv is None else argv
     try:
-        opts, rest, extra = parse_options(argv, reader_options=True)
+        opts, rest, extra = parse_options(argv, reader_options=True, bam_options=True)
     except Exception as e:                                  # getopt's and ours
         print(f"hsa_amd.align: {e}", file=sys.stderr)
         return 1
     if len(rest) < 2:
-        print("usage: python -m hsa_amd.align [bwa-aln options] [--header] [--unaligned FILE] [--splice] [-f OUT] <prefix> <in.fq>",
+        print("usage: python -m hsa_amd.align [bwa-aln options] [--header] [--unaligned FILE] [--splice] [-f OUT] <prefix> <in.fq | -b in.bam>",
               file=sys.stderr)
         return 1
     gi, chrs = open_index64(rest[0])
@@ -667,6 +773,9 @@ def main(argv=None) -> int:
             out.write(sam_header(rest[0]))
         _, stats = align_fastq(gi, chrs, rest[1], opts, out, unaligned=un, splice=extra.get("splice", False))
         out.flush()
+    except bam.BamError as e:                               # a file that is not BAM
+        print(f"hsa_amd.align: {e}", file=sys.stderr)
+        return 1
     finally:
         if un:
             un.close()
@@ -676,6 +785,9 @@ def main(argv=None) -> int:
     if opts["trim_qual"] >= 1 and stats["total_bases"]:       # bwaseqio.c:224-225
         print(f"[hsa_amd.align] {100.0 * stats['trimmed_bases'] / stats['total_bases']:.1f}% bases are trimmed.", file=sys.stderr)
     print("[hsa_amd.align] " + ", ".join(f"{k} {v}" for k, v in stats.items() if k != "refused_names"), file=sys.stderr)
+    if stats.get("bam_truncated"):                            # the reads before it are aligned (bam_read1 < 0 ends the reference's loop)
+        print("hsa_amd.align: the BAM input ends in a truncated or inconsistent record", file=sys.stderr)
+        return 1
     return 0
 
 

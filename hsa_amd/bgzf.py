@@ -5,7 +5,8 @@ A BGZF file is a series of independent gzip members of at most 64 KB, each with 
 like any other gzip file.  scan() walks the members on the host (nothing is inflated for it),
 inflate_device() uploads the file's bytes and runs hsa_inflate_bgzf_device, one wavefront per
 block, and read_input() opens a file as the readers take it: plain, BGZF or general gzip.
-hsa_amd.align and hsa_amd.index_build do not call it yet ("BGZF input").
+hsa_amd.bam.open_text reads a BAM file through it (`hsa_amd.align -b`); FASTQ and FASTA in front
+of hsa_amd.align and hsa_amd.index_build do not go through it yet ("BGZF input").
 
 A block the device refuses (any status but HSA_INF_OK) is inflated again on the host with
 zlib, which also decides whether the file is corrupt: the errors are zlib's and the CRC and

@@ -86,7 +86,8 @@
 // rd_trim).  A trimmed read keeps its bytes: hsa_job_t.len is the trimmed length, d_full_len
 // the stored one.  With a filter one more scan (the records the reader keeps) and k_rd_limit
 // end the load behind the max_records-th kept record.  hsa_reads_device refuses the options
-// (HSA_E_ARG) and then runs the same code.  Not built: BAM input (-b).
+// (HSA_E_ARG) and then runs the same code.  BAM input (-b) is hsa_bam_reads_device's
+// (hsa_bam.hip); both calls here refuse its mode bits.
 #include <algorithm>
 #include <cstring>
 #include <hip/hip_runtime.h>
@@ -94,26 +95,19 @@
 #include <string.h>
 
 #include "hsa_internal.h"
+#include "hsa_rd_wave.h"
+#include "hsa_rd_tail.h"
 
 #define RD_ONES32 0xFFFFFFFFu
 #define RD_RT 16u                      // records per wavefront of k_rd_record and k_rd_bytes
 #define RD_REFUSED_MODE 0xFF0003E8u   // barcode length, IL13, BAM*, CFY (bwtaln.h:122-131): hsa_reads_device takes none
 #define RD_MODE_CFY 0x08u             // bwtaln.h:125
 #define RD_MODE_IL13 0x200u           // :131
-#define RD_MODE_BAM 0x1E0u            // :127-130: not built
+#define RD_MODE_BAM 0x1E0u            // :127-130: hsa_bam_reads_device
 #define RD_MAX_BCLEN 63u              // BWA_MAX_BCLEN, bwtaln.h:28
-#define RD_MIN_RDLEN 35u              // BWA_MIN_RDLEN, bwtaln.h:26
 // bwa_trim_read's sum: a byte of 33..127, 31 off with IL13, gives q - 33 in -31..94, so a
 // step adds between trim_qual - 94 and trim_qual + 31 and |s| <= HSA_RD_MAX_LEN * (trim_qual + 94)
 #define RD_MAX_TRIM ((int32_t)(0x7FFFFFFFu / HSA_RD_MAX_LEN) - 94)
-#define RD_FL_FILTERED 0x80u          // r_fl between k_rd_record and k_rd_keep: the reader skips the record
-
-struct Rd3 {
-    uint64_t j, c, n;       // jobs, code bytes, name bytes
-};
-struct Rd3Plus {
-    __host__ __device__ Rd3 operator()(const Rd3 &a, const Rd3 &b) const { return Rd3{a.j + b.j, a.c + b.c, a.n + b.n}; }
-};
 
 struct RdArgs {
     const uint8_t *in;
@@ -229,26 +223,6 @@ __device__ __forceinline__ uint32_t rd_code(uint32_t c)
     return l == 'a' ? 0u : l == 'c' ? 1u : l == 'g' ? 2u : l == 't' ? 3u : c == '-' ? 5u : 4u;
 }
 
-// The inclusive sum and the maximum over a wavefront's 64 lanes; every lane calls.
-__device__ __forceinline__ int32_t rd_wave_scan(int32_t v, uint32_t lane)
-{
-#pragma unroll
-    for (uint32_t d = 1u; d < 64u; d <<= 1) {
-        const int32_t t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-__device__ __forceinline__ int32_t rd_wave_max(int32_t v)
-{
-#pragma unroll
-    for (uint32_t d = 32u; d; d >>= 1) {
-        const int32_t t = __shfl_xor(v, (int)d, 64);
-        v = t > v ? t : v;
-    }
-    return v;
-}
-
 // The Casava filter (bwaseqio.c:176-181) on a comment of n bytes: it is a C string, so a NUL
 // before the first ':' ends the search; the byte after that ':' must be 'Y'.  Called by the
 // whole wave with the same c and n.
@@ -268,39 +242,11 @@ __device__ __forceinline__ bool rd_casava(const uint8_t *c, uint32_t n, uint32_t
 }
 
 // bwa_trim_read (bwaseqio.c:92-103) on the quality bytes q[0, len), qshift taken off each:
-// the length the read keeps.  The reference walks l from len - 1 down to RD_MIN_RDLEN with
-// s += trim_qual - (q[l] - 33), ends at the first s < 0, and cuts at the l of the first
-// strictly greater s.  Here 64 steps of the walk at a time, lane i at step p0 + i: a
-// wave-wide inclusive sum on top of the carried one gives every step's s, a ballot the
-// first negative one (the steps from there on do not count), a maximum over the steps
-// before it the chunk's best s, and the lowest lane that holds it the largest l of equal
-// maxima.  The carry (sum, best, best_l) and the trip count are the same in all lanes.
+// the length the read keeps (rd_trim_walk, hsa_rd_wave.h, which the BAM loader shares).
 // |s| <= len * (trim_qual + 94) fits int32 for trim_qual <= RD_MAX_TRIM.
 __device__ __forceinline__ uint32_t rd_trim(const uint8_t *q, uint32_t len, int32_t trim_qual, uint32_t qshift, uint32_t lane)
 {
-    if (len <= RD_MIN_RDLEN) return len;
-    const uint32_t steps = len - RD_MIN_RDLEN;
-    int32_t sum = 0, best = 0;
-    uint32_t best_l = len;
-    for (uint32_t p0 = 0; p0 < steps; p0 += 64u) {
-        const uint32_t p = p0 + lane;
-        const bool on = p < steps;
-        const uint32_t l = len - 1u - (on ? p : 0u);          // (a lane without a step loads the last byte)
-        const int32_t qv = (int32_t)q[l] - (int32_t)qshift - 33;
-        const int32_t s = sum + rd_wave_scan(on ? trim_qual - qv : 0, lane);
-        const unsigned long long neg = __ballot(on && s < 0);
-        const uint32_t stop = neg ? (uint32_t)__ffsll((long long)neg) - 1u : 64u;
-        const bool counts = on && lane < stop;
-        const int32_t top = rd_wave_max(counts ? s : (int32_t)0x80000000);
-        const unsigned long long at_top = __ballot(counts && s == top);
-        if (top > best) {
-            best = top;
-            best_l = len - (p0 + (uint32_t)__ffsll((long long)at_top));      // len - 1 - step
-        }
-        if (neg) break;
-        sum = __shfl(s, 63, 64);
-    }
-    return best_l;
+    return rd_trim_walk([=](uint32_t l) { return (int32_t)q[l] - (int32_t)qshift - 33; }, len, trim_qual, lane);
 }
 
 // One wavefront per RD_RT consecutive records, the lanes along the bytes of a record's
@@ -420,55 +366,10 @@ __global__ void __launch_bounds__(256) k_rd_limit(RdArgs a)
     if (k < a.M && a.unf[k] && a.unf_scan[k] + 1u == a.max_rec) a.g[3] = k + 1u;
 }
 
-__global__ void __launch_bounds__(256) k_rd_max(RdArgs a)
-{
-    __shared__ uint32_t sMax;
-    if (threadIdx.x == 0) sMax = 0u;
-    __syncthreads();
-    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    if (k < rd_loaded(a, rd_shape(a)) && a.r_fl[k] != RD_FL_FILTERED) atomicMax(&sMax, a.r_len[k]);
-    __syncthreads();
-    if (threadIdx.x == 0 && sMax) atomicMax(&a.g[1], sMax);
-}
+// The tail that does not depend on the format (hsa_rd_tail.h, shared with hsa_bam.hip)
+__global__ void __launch_bounds__(256) k_rd_max(RdArgs a) { rd_tail_max(a, [&] { return rd_loaded(a, rd_shape(a)); }); }
 
-// bwtaln.c:273-274: local_opt.max_diff before the option switch
-__device__ __forceinline__ int32_t rd_threshold(const RdArgs &a)
-{
-    return a.maxdiff ? a.maxdiff[a.g[1] > a.len_floor ? a.g[1] : a.len_floor] : a.max_diff;
-}
-
-__global__ void __launch_bounds__(256) k_rd_keep(RdArgs a)
-{
-    __shared__ uint32_t sMax, sTrim, sTotal;               // (a block's bases: 256 reads of at most 65 535)
-    if (threadIdx.x == 0) sMax = sTrim = sTotal = 0u;
-    __syncthreads();
-    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    if (k <= a.M) {
-        Rd3 v{0, 0, 0};
-        if (k < rd_loaded(a, rd_shape(a))) {
-            const uint32_t fl = a.r_fl[k], len = a.r_len[k];
-            const uint32_t full = a.r_full ? a.r_full[k] : len;             // the code and quality bytes stay whole
-            const uint32_t st = fl == RD_FL_FILTERED ? HSA_RD_FILTERED : (int64_t)a.r_nn[k] > (int64_t)rd_threshold(a) ? HSA_RD_NDROP
-                                : fl ? HSA_RD_POLYAT : HSA_RD_SEARCHED;
-            a.r_fl[k] = st;
-            if (st == HSA_RD_SEARCHED) {
-                v = Rd3{1u, full, a.r_name_len[k]};
-                atomicMax(&sMax, len);
-            }
-            if (a.octr && st != HSA_RD_FILTERED) {                          // bwaseqio.c:204, :210: every read returned
-                atomicAdd(&sTotal, full);
-                if (full != len) atomicAdd(&sTrim, full - len);
-            }
-        }
-        a.s_in[k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && sMax) atomicMax(&a.g[2], sMax);
-    if (threadIdx.x == 0 && sTotal) {                                       // (sums: any order gives the same)
-        atomicAdd(&a.octr[3], (unsigned long long)sTotal);
-        if (sTrim) atomicAdd(&a.octr[2], (unsigned long long)sTrim);
-    }
-}
+__global__ void __launch_bounds__(256) k_rd_keep(RdArgs a) { rd_tail_keep(a, [&] { return rd_loaded(a, rd_shape(a)); }); }
 
 __global__ void __launch_bounds__(256) k_rd_rows(RdArgs a)
 {
@@ -476,27 +377,7 @@ __global__ void __launch_bounds__(256) k_rd_rows(RdArgs a)
     const RdShape sh = rd_shape(a);
     const uint32_t loaded = rd_loaded(a, sh);
     const Rd3 tot = a.s_out[a.M];
-    if (k < loaded) {
-        const uint32_t st = a.r_fl[k], len = a.r_len[k];
-        const Rd3 at = a.s_out[k];
-        const bool kept = st == HSA_RD_SEARCHED;
-        uint32_t *row = a.rec + (size_t)HSA_RD_ROW_WORDS * k;
-        const bool skipped = st == HSA_RD_FILTERED;          // (no read: no length, no count)
-        row[0] = st; row[1] = skipped ? 0u : len; row[2] = skipped ? 0u : a.r_nn[k]; row[3] = kept ? (uint32_t)at.j : RD_ONES32;
-        if (kept && at.j <= a.job_cap) {
-            a.name_off[at.j] = at.n;
-            a.qual_off[at.j] = at.c;
-            if (at.j < a.job_cap) {
-                hsa_job_t jb;
-                jb.off = at.c; jb.len = len;
-                jb.max_diff = a.maxdiff ? a.maxdiff[len] : a.max_diff;                    // bwtaln.c:330-331
-                jb.seed_len = a.seed_len < (int32_t)len ? a.seed_len : 0x7fffffff;        // :332
-                jb.regime = a.regime;
-                a.jobs[at.j] = jb;
-                if (a.full_len) a.full_len[at.j] = a.r_full ? a.r_full[k] : len;
-            }
-        }
-    }
+    if (k < loaded) rd_tail_row(a, k);
     if (k == 0u) {
         if (tot.j <= a.job_cap) { a.name_off[tot.j] = tot.n; a.qual_off[tot.j] = tot.c; }
         const uint32_t bad = a.g[0];
@@ -577,7 +458,7 @@ extern "C" int hsa_reads_device(hsa_index_t *ix, const hsa_reads_batch_t *b, voi
 {
     if (ix && b && (b->trim_qual != 0 || (b->mode & RD_REFUSED_MODE))) {
         hsa_set_error("hsa_reads_device: quality trimming, barcodes, the Casava filter and Illumina-1.3 qualities are "
-                      "hsa_reads_device_opts'; BAM input is not built");
+                      "hsa_reads_device_opts'; BAM input is hsa_bam_reads_device's");
         return HSA_E_ARG;
     }
     return hsa_reads_device_opts(ix, b, stream);
@@ -607,7 +488,7 @@ extern "C" int hsa_reads_device_opts(hsa_index_t *ix, const hsa_reads_batch_t *b
     const bool filter = (b->mode & RD_MODE_CFY) != 0u || bc_len != 0u;
     const bool opt = filter || b->trim_qual >= 1 || (b->mode & RD_MODE_IL13) != 0u;
     if (b->mode & RD_MODE_BAM) {
-        hsa_set_error("%s: BAM input is not built", what);
+        hsa_set_error("%s: BAM input is hsa_bam_reads_device's", what);
         return HSA_E_ARG;
     }
     if (b->trim_qual > RD_MAX_TRIM || bc_len > RD_MAX_BCLEN || b->rec_cap > (1u << 28)) {

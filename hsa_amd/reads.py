@@ -11,7 +11,8 @@ Two ways to the same reads:
   outputs, runs the call, and runs it again with the counters' sizes when room was short.
 
 Both take the reader's options: quality trimming (-q), barcodes (-B), the Casava filter (-Y)
-and Illumina-1.3 qualities (-I), as bwa_read_seq applies them.  Not restated: BAM input (-b).
+and Illumina-1.3 qualities (-I), as bwa_read_seq applies them.  BAM input (-b) is hsa_amd.bam's:
+bwa_read_bam takes none of these options but the trimming.
 An input that ends in a lone header character reads as
 ended (the reference's answer there depends on the file size modulo its 4 096-byte buffer)."""
 from __future__ import annotations

@@ -34,6 +34,9 @@
  *   hsa_inflate_bgzf_device -- gzread (zlib's inflate with the gzip trailer's CRC32 check) for
  *                         the members of a BGZF file whose bytes sit in device memory: the
  *                         step in front of hsa_reads_device and hsa_fasta_device.
+ *   hsa_bam_reads_device -- bwa_read_bam (bwaseqio.c:105-157, without its line 142) for the
+ *                         inflated bytes of a BAM file in device memory: hsa_reads_device's
+ *                         outputs.
  *   hsa_extend_batch   -- bwt_extend_backward / bwt_extend_foreward (bwtgap.c:640-663,
  *                         bwt_backtracing_search :346-511): the splice path's seed
  *                         extensions.
@@ -1015,7 +1018,7 @@ int hsa_sam_merge_device(hsa_index_t *ix, const hsa_sam_merge_batch_t *b, void *
  * d_opt_counters (>= HSA_RD_OPT_COUNTERS u64, or NULL): [0] records loaded, the skipped ones
  * included (the rows written), [1] records skipped, [2] bases trimmed and [3] bases in all, over
  * the loaded records not skipped (the reference's "% bases are trimmed").  BAM input (mode &
- * 0x1e0) is not built: HSA_E_ARG. */
+ * 0x1e0) is hsa_bam_reads_device's: HSA_E_ARG here. */
 #define HSA_RD_SEARCHED 0u
 #define HSA_RD_NDROP    1u    /* more codes above 3 than the threshold */
 #define HSA_RD_POLYAT   2u    /* the first 15 codes all A or all T */
@@ -1196,6 +1199,89 @@ typedef struct {
     uint64_t *d_counters;            /* HSA_INF_COUNTERS */
 } hsa_inflate_batch_t;
 int hsa_inflate_bgzf_device(int device, const hsa_inflate_batch_t *b, void *stream);
+
+/* ---- BAM bytes to a search batch ----
+ * bwa_read_bam (bwaseqio.c:105-157) for the inflated bytes of a BAM file in device memory,
+ * with one departure: line 142, which reverses the read "to be reversed back in
+ * bwa_refine_gapped", is not applied (the reverse-back is commented out in this reference,
+ * bwtse.c:545).  A record then gives the read the FASTQ reader gives for the same bases, and
+ * the call leaves exactly what hsa_reads_device_opts leaves: d_jobs, d_codes (16 zero bytes
+ * behind the last read), names and qualities (always present) with their offsets, d_full_len,
+ * the rows of d_rec (HSA_RD_SEARCHED / NDROP / POLYAT / FILTERED), d_counters [0..15] and
+ * d_opt_counters in the same slots.  d_in[0] must be the first byte of a record (the header is
+ * the caller's: hsa_amd/bam.py, read_header).
+ *
+ * Per record: taken when (which & 1 and FLAG 0x40) or (which & 2 and FLAG 0x80) or (which & 4
+ * and neither), bwaseqio.c:118-121; nothing else in FLAG filters, secondary and supplementary
+ * records are read.  A record not taken, and one with l_seq == 0, gets a row of status
+ * HSA_RD_FILTERED and counts towards no batch.  Bases through bam_nt16_nt4_table (1, 2, 4, 8
+ * are 0..3, all else 4), qualities q + 33 capped at 126 (0xFF gives '~'); with FLAG 0x10 the
+ * codes are reverse-complemented and the qualities reversed before anything else looks at
+ * them; trim_qual >= 1 trims with bwa_trim_read from the read's own end after that.  The name
+ * is the l_read_name bytes up to the first NUL; no "/1" is cut.  Filter, max_diff, seed_len
+ * and threshold as hsa_reads_device states them.
+ *
+ * Finding the records.  A record is block_size (u32) and that many bytes, so the starts form a
+ * chain.  d_anchor holds n_anchor >= 1 ascending offsets: [0] must be 0, a true record start;
+ * the others are offsets at which the caller expects a record to start (the first bytes of
+ * BGZF members).  Segment i, [anchor i, anchor i + 1), is walked on its own; every hop is
+ * checked before it is taken (l_read_name >= 1, block_size >= 32 + l_read_name + 4 n_cigar +
+ * (l_seq + 1) / 2 + l_seq, the record ends inside the text), so a walk that began inside a
+ * record looks at no byte outside the text and advances by 37 bytes or more per hop (the
+ * staging loads whole aligned 16-byte units: up to 15 bytes before d_in and behind d_in + n_in,
+ * inside the allocation's granule, are loaded and never looked at).  Segment i
+ * is verified when its walk lands exactly on anchor i + 1, or, the last one, on the end of
+ * the text (with or without at_eof: the text then ends at a record boundary).  By induction from anchor 0 the records of the longest verified prefix
+ * are exact, and so is the walk of the first segment that is not verified (it began at a true
+ * start); everything behind it is discarded and the load ends there (HSA_BAM_END_ANCHOR): the
+ * caller goes on from [10] with a single anchor.  Anchors that do not ascend end the same way.
+ *
+ * The first record the device does not take (an empty name, a read over HSA_RD_MAX_LEN, or,
+ * with a table, of n_maxdiff bases or more) stops the load as hsa_reads_device's first
+ * non-canonical record does: [11] and [12] name it and its offset.  [10], the bytes consumed,
+ * is always a true record start.  At most rec_cap records (0: max_records) are looked at,
+ * the rows d_rec holds, and the load ends behind the max_records-th record that is a read.
+ * d_bam_counters (HSA_BAM_COUNTERS u64): [0] why the load ended (HSA_BAM_END_*), [1] segments
+ * verified, [2] records the exact walks found, [3] the offset at which they ended.
+ * HSA_E_ARG: null pointers, n_anchor == 0, which outside 1..7, n_in >= 2^32 - 256, and what
+ * hsa_reads_device_opts refuses of the arguments they share.  Scratch and timer are the
+ * handle's, shared with hsa_reads_device. */
+#define HSA_BAM_END_MAX        0u   /* max_records reads, or rec_cap records, loaded */
+#define HSA_BAM_END_INPUT      1u   /* the end of the input */
+#define HSA_BAM_END_INCOMPLETE 2u   /* an incomplete last record with at_eof == 0 */
+#define HSA_BAM_END_ANCHOR     3u   /* an anchor is not on the chain */
+#define HSA_BAM_END_HOST       4u   /* a record for the host: [11], [12] */
+#define HSA_BAM_END_MALFORMED  5u   /* an inconsistent record, or with at_eof a truncated one, at [10] */
+#define HSA_BAM_COUNTERS 4
+typedef struct {
+    const uint8_t *d_in; uint64_t n_in;
+    int32_t at_eof;
+    uint32_t max_records;
+    uint32_t which;                  /* 1..7 */
+    int32_t trim_qual;
+    int32_t max_diff;
+    const int32_t *d_maxdiff; uint32_t n_maxdiff;
+    uint32_t len_floor;
+    int32_t seed_len;
+    int32_t regime;
+    const uint64_t *d_anchor; uint32_t n_anchor;
+    hsa_job_t *d_jobs; uint64_t job_cap;
+    uint8_t *d_codes; uint64_t code_cap;
+    uint8_t *d_names; uint64_t name_cap; uint64_t *d_name_off;
+    uint8_t *d_quals; uint64_t qual_cap; uint64_t *d_qual_off;
+    uint32_t *d_full_len;            /* job_cap u32 */
+    uint32_t *d_rec; uint32_t rec_cap;
+    uint64_t *d_counters;            /* >= 16 u64 */
+    uint64_t *d_opt_counters;        /* >= HSA_RD_OPT_COUNTERS u64 */
+    uint64_t *d_bam_counters;        /* >= HSA_BAM_COUNTERS u64 */
+} hsa_bam_batch_t;
+int hsa_bam_reads_device(hsa_index_t *ix, const hsa_bam_batch_t *b, void *stream);
+/* The HSA_BAM_LAUNCHES times in ms of the handle's last timed call (hsa_bam_timing):
+ * k_bam_walk (with the memsets), the segment scan, k_bam_starts, k_bam_record, k_bam_max
+ * with k_bam_keep, the record scan, k_bam_rows, k_bam_bytes. */
+#define HSA_BAM_LAUNCHES 8
+void hsa_bam_timing(int on);
+int hsa_bam_launch_times(hsa_index_t *ix, float *ms);
 
 #ifdef __cplusplus
 }
