@@ -16,7 +16,7 @@ REFOBJS   = bwtaln bwtgap BWT BWTConstruct utils dictionary DNACount HSP inipars
 OBJS      = $(addprefix $(OUT)/obj/,$(addsuffix .o,$(REFOBJS)))
 
 all: $(OUT)/HSA $(OUT)/ref_probe $(OUT)/ref_mgcap $(OUT)/ref_extcap $(OUT)/HSA_gpu $(OUT)/HSA_gpu_mg $(OUT)/HSA_gpu_all \
-     $(OUT)/ref_probe_gpu $(OUT)/HSA_sam
+     $(OUT)/ref_probe_gpu $(OUT)/HSA_sam $(OUT)/ref_refine
 
 $(OUT)/obj/%.o: $(REF)/%.c
 	@mkdir -p $(OUT)/obj
@@ -33,6 +33,17 @@ $(OUT)/HSA: $(OUT)/obj/main.o $(OUT)/libhsaref.a
 $(OUT)/ref_probe: ref_probe.c $(OUT)/libhsaref.a
 	$(CC) $(REFFLAGS) -I$(REF) ref_probe.c $(OUT)/libhsaref.a \
 	    -Wl,--wrap=bwt_splice_match -lm -lz -o $@
+
+# ref_refine.c is ours; it calls the reference's bwa_refine_gapped on fabricated rows
+# (tools/make_golden_refine.py, tests/refine_cases.py).
+$(OUT)/ref_refine: ref_refine.c $(OUT)/libhsaref.a
+	$(CC) $(REFFLAGS) -I$(REF) ref_refine.c $(OUT)/libhsaref.a -lm -lz -o $@
+
+# ... and once under the sanitizers (not part of all): the driver's own code instrumented,
+# the reference's objects as above; run as a stand-alone program on the whole case set.
+$(OUT)/ref_refine_san: ref_refine.c $(OUT)/libhsaref.a
+	$(CC) -g -O1 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    -fgnu89-inline -I$(REF) ref_refine.c $(OUT)/libhsaref.a -lm -lz -o $@
 
 # HSA_gpu: the reference's own HSA binary with OUR bwa_cal_sa_reg_gap linked in
 # (INTEGRATION.md).  The reference definition is weakened in a copy of bwtaln.o

@@ -7,7 +7,12 @@
 * past 2^32, where no reference exists: validity of every answered row against the text,
   exactness by translating each row's window into a small text (whose side the SAM tests
   pin to the reference), and the text's end;
-* the contract's edges on small fabricated batches."""
+* the contract's edges on small fabricated batches;
+* against the compiled reference's own bwa_refine_gapped on fabricated rows: the committed
+  fixture tests/golden/refine_cases.npz (tests/refine_cases.py: ties inside repeats, long
+  deletions across the band's 64-column chunks, indels at the ends, N, odd lengths, windows
+  cut by the text's end, every text alignment), field for field, in three batch layouts,
+  and a fresh random set where the reference's driver is built."""
 import ctypes as C
 import gzip
 import json
@@ -18,6 +23,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import refine_cases as rc
 from golden_io import GOLD, INDEX, parse_opts
 from hsa_amd import index_io
 from hsa_amd.chain import to_device as dev
@@ -27,6 +33,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HSA = os.path.join(ROOT, "oracle", "_ref", "HSA")
+REF_REFINE = os.path.join(ROOT, "oracle", "_ref", "ref_refine")
 MAN = json.load(open(os.path.join(GOLD, "manifest_dropin.json")))
 U64 = np.uint64
 ONES = U64(0xFFFFFFFFFFFFFFFF)
@@ -406,24 +413,25 @@ def test_no_rows_return_cleanly():
         assert not out["ctr"][:7].any() and (out["rows"] == 0x77).all()
 
 
-def test_longest_read_and_widest_gap_of_the_layout_are_answered():
-    """len 1023 with a gap count of 16, both strands: answered, and valid."""
-    from hsa_amd import _lib, synth
-    gi = index_text("tiny")
-    text = index_io.read_pac(INDEX["tiny"])
-    fw = np.concatenate([text[20000:20400], text[20416:21039]]).astype(np.uint8)      # a 16 bp deletion
-    ins = np.random.default_rng(5).integers(0, 4, 16).astype(np.uint8)
-    rv = synth.revcomp_codes(np.concatenate([text[30000:30500], ins, text[30500:31007]]).astype(np.uint8))
-    assert len(fw) == 1023 == len(rv)
-    t, host = fabricate([1023, 1023], np.concatenate([fw, rv]), [(0, 0, 16, 20000, 20001), (1, 1, 16, 30000, 30001)])
+def test_longest_read_and_widest_gap_of_the_layout_are_answered(golden_side):
+    """len 1023 with a gap count of 16, a deletion and an insertion on both strands: answered
+    with the reference's own strings (the fixture's `longest` rows), and valid."""
+    from hsa_amd import _lib
+    gi, text = golden_side
+    long = [r for r in rc.golden()[2] if r["family"].startswith("longest")]
+    assert sorted((r["strand"], "16D" in r["made"], r["len"], r["gap"]) for r in long) == \
+        [(0, False, 1023, 16), (0, True, 1023, 16), (1, False, 1023, 16), (1, True, 1023, 16)]
+    t, host = golden_batch(long)
     out = refine(gi, t, cigar_stride=16, md_stride=256)
-    assert [int(s) for s in out["rows"][:, 0]] == [0, 0] and int(out["ctr"][6]) == 2 and int(out["ctr"][4]) == 0
-    assert re.fullmatch(r"\d+M16D\d+M", row_strings(out, 0)["cigar"]) and row_strings(out, 0)["nm"] == 16
-    assert re.fullmatch(r"\d+M16I\d+M", row_strings(out, 1)["cigar"])
-    for k in (0, 1):
-        replay(out, k, oriented(host, k, k), lambda p: text[p])
+    assert [int(s) for s in out["rows"][:, 0]] == [0] * 4 and int(out["ctr"][6]) == 4 and int(out["ctr"][4]) == 0
+    for k, r in enumerate(long):
+        rs = row_strings(out, k)
+        assert (rs["cigar"], rs["nm"], rs["md"]) == (r["cigar"], r["nm"], r["md"]), (r["made"], rs, r["cigar"], r["md"])
+        replay(out, k, oriented(host, k, r["strand"]), lambda p: text[p])
+    assert any("16D" in r["cigar"] for r in long) and any("16I" in r["cigar"] for r in long)
     # past the layout: a gap count of HSA_RF_MAX_GAP + 1 is refused, not approximated
-    t2, _ = fabricate([1023], fw, [(0, 0, _lib.HSA_RF_MAX_GAP + 1, 20000, 20001)])
+    r = long[0]
+    t2, _ = fabricate([1023], r["codes"], [(0, r["strand"], _lib.HSA_RF_MAX_GAP + 1, r["pos"], r["ori"])])
     assert int(refine(gi, t2)["rows"][0, 0]) == _lib.HSA_RF_CAP
 
 
@@ -583,8 +591,9 @@ def test_text_end_is_the_same_on_both_sides(big_text64):
     """Rows at the last characters of the text, on the 4.3 Gbp text and on a 400-character
     text that ends the same way: gapped rows whose window the text's end cuts
     (bwtse.c:393), down to one character, and ungapped rows that end at and past it
-    (HSA_RF_TEXT).  Self-consistency only: the reference's lines never show a window cut
-    by the text's end, so no reference output pins these rows."""
+    (HSA_RF_TEXT).  The two sides must agree; the small side's cut windows are pinned to the
+    reference's bwa_refine_gapped by the fixture's `cut` rows (test_golden_rows_equal_the_reference),
+    which this test carries past 2^32."""
     from hsa_amd import _lib, synth
     gi, genome = big_text64
     T = BIG_T
@@ -611,3 +620,131 @@ def test_text_end_is_the_same_on_both_sides(big_text64):
     assert st[:4] == [0, _lib.HSA_RF_TEXT, 0, 0] and st[4:9] == [0] * 5 and st[9] == _lib.HSA_RF_TEXT and st[10:] == [0] * 4
     assert re.fullmatch(r"\d+M2D\d+M", row_strings(a, 4)["cigar"]) and row_strings(a, 4)["nm"] == 2
     sgi.close()
+
+
+# ---------------------------------------------------------------- against bwa_refine_gapped itself
+@pytest.fixture(scope="module")
+def golden_side():
+    """A handle whose text is the fixture's text: (index, text)."""
+    text = rc.golden()[0]["text"]
+    gi, starts = small_side([text])
+    assert int(starts[0]) == 0
+    yield gi, text
+    gi.close()
+
+
+def golden_batch(rows, per_read=None):
+    """fabricate() of fixture rows, one read per row; per_read(r) gives a read's rows as
+    (strand, gap, pos, ori) when it has more than its own."""
+    lens = [r["len"] for r in rows]
+    codes = np.concatenate([r["codes"] for r in rows]).astype(np.uint8)
+    per_read = per_read or (lambda r: [(r["strand"], r["gap"], r["pos"], r["ori"])])
+    return fabricate(lens, codes, [(k, *x) for k, r in enumerate(rows) for x in per_read(r)])
+
+
+def differences(out, rows, at=None):
+    """The rows of `out` (row at[k] for fixture row k) that are not the reference's, each as
+    a line naming the family and both CIGARs."""
+    from hsa_amd import _lib, refine as rf
+    bad = []
+    for k, r in enumerate(rows):
+        t = k if at is None else at[k]
+        st, n_cigar, nm, md_len, trim5, trim3 = (int(x) for x in out["rows"][t, :6])
+        n_ops = min(n_cigar, out["cigar"].shape[1])
+        got = dict(status=st, n_cigar=n_cigar, words=[int(w) for w in out["cigar"][t, :n_ops]], nm=nm, md_len=md_len,
+                   md=out["md"][t, :min(md_len, out["md"].shape[1])].tobytes(), trim5=trim5, trim3=trim3,
+                   rpos=(int(out["rpos"][t, 0]), int(out["rpos"][t, 1])))
+        want = dict(status=_lib.HSA_RF_OK, n_cigar=len(r["words"]), words=[int(w) for w in r["words"]], nm=r["nm"],
+                    md_len=len(r["md"]), md=r["md"].encode(), trim5=r["trim5"], trim3=r["trim3"],
+                    rpos=(r["occ_pos"], r["ori_pos"]))
+        if got != want:
+            fields = [f for f in want if got[f] != want[f]]
+            bad.append(f"case {r['k']} {r['family']} len {r['len']} gap {r['gap']} strand {r['strand']} pos {r['pos']}: "
+                       f"device {rf.cigar_text(got['words'])} reference {r['cigar']} (made {r['made'] or '-'}); differ in "
+                       + ", ".join(f"{f} {got[f]!r} != {want[f]!r}" for f in fields if f != "words"))
+    return bad
+
+
+def check_against_reference(gi, rows):
+    """Every row refined on `gi` is the reference's: status, n_cigar, CIGAR words, NM, md_len,
+    MD bytes, trim5 == start, trim3 == len - 1 - end, rpos == (occ_pos, ori_pos).  The strides
+    are the set's longest CIGAR and MD, so HSA_RF_MD would be a difference too."""
+    t, _ = golden_batch(rows)
+    out = refine(gi, t, cigar_stride=max(len(r["words"]) for r in rows), md_stride=max(len(r["md"]) for r in rows))
+    assert int(out["ctr"][0]) == len(rows) and int(out["ctr"][6]) == sum(r["gap"] > 0 for r in rows)
+    bad = differences(out, rows)
+    fams = sorted({b.split()[2] for b in bad})
+    assert not bad, f"{len(bad)} of {len(rows)} rows differ from the reference, families {fams}:\n" + "\n".join(bad[:12])
+    assert [int(x) for x in out["ctr"][1:6]] == [len(rows), 0, 0, 0, 0]
+    return out
+
+
+def test_golden_rows_equal_the_reference(golden_side):
+    """Every row of the committed fixture, none skipped."""
+    gi, _ = golden_side
+    rows = rc.golden()[2]
+    assert len(rows) == 2104
+    check_against_reference(gi, rows)
+
+
+def test_golden_rows_do_not_depend_on_the_layout(golden_side):
+    """The 100-base rows in a batch of their own (max_len 100) and in a batch that also holds
+    the 1023-base rows (another tb_stride, ring and win_cap): identical outputs, and the
+    reference's in both."""
+    gi, _ = golden_side
+    rows = rc.golden()[2]
+    short = [r for r in rows if r["len"] == 100]
+    long = [r for r in rows if r["len"] == 1023]
+    assert len(short) == 1888 and len(long) == 16
+    cs, ms = max(len(r["words"]) for r in rows), max(len(r["md"]) for r in rows)
+    ta, _ = golden_batch(short)
+    tb, _ = golden_batch(short + long)
+    assert ta["max_len"] == 100 and tb["max_len"] == 1023
+    a, b = refine(gi, ta, cigar_stride=cs, md_stride=ms), refine(gi, tb, cigar_stride=cs, md_stride=ms)
+    n = len(short)
+    for k in ("rows", "rpos", "cigar", "md"):
+        assert np.array_equal(a[k][:n], b[k][:n]), k
+    for out in (a, b):
+        bad = differences(out, short)
+        assert not bad, f"{len(bad)} rows differ from the reference:\n" + "\n".join(bad[:12])
+
+
+def test_golden_rows_do_not_depend_on_their_place(golden_side):
+    """max_occ-style multiplicity: every 100-base read with three rows -- its own, the same
+    position on the other strand, its own again -- so that both strands of one read are
+    adjacent in the row list.  Each row answers as it does alone (the same rows, one read
+    each), and the read's own rows as the reference does."""
+    gi, _ = golden_side
+    short = [r for r in rc.golden()[2] if r["len"] == 100]
+
+    def three(r):
+        own = (r["strand"], r["gap"], r["pos"], r["ori"])
+        return [own, (1 - r["strand"], r["gap"], r["pos"], r["ori"]), own]
+
+    tm, _ = golden_batch(short, per_read=three)
+    alone = [dict(r, strand=s, gap=g, pos=p, ori=o) for r in short for s, g, p, o in three(r)]
+    t1, _ = golden_batch(alone)
+    assert tm["n_jobs"] == len(short) and t1["n_jobs"] == 3 * len(short) == tm["pos_cap"] == t1["pos_cap"]
+    # (the other strand's rows are no alignments of anything: their CIGARs run long)
+    m, one = refine(gi, tm, cigar_stride=64, md_stride=256), refine(gi, t1, cigar_stride=64, md_stride=256)
+    assert same(m, one)
+    for slot in (0, 2):
+        bad = differences(m, short, at=[3 * k + slot for k in range(len(short))])
+        assert not bad, f"{len(bad)} rows differ from the reference:\n" + "\n".join(bad[:12])
+
+
+@pytest.mark.skipif(not os.path.exists(REF_REFINE), reason="oracle/_ref/ref_refine not built (make -C oracle)")
+def test_random_rows_equal_the_reference_run_here(tmp_path):
+    """A seeded random set from the same families -- another seed, a text with other motifs
+    and stretch lengths, offsets moved, other read lengths -- answered by the reference's
+    driver here and compared in the same fields."""
+    c = rc.generate(seed=977, vary=True)
+    g = rc.golden()[0]
+    assert len(c["text"]) != len(g["text"]) and not np.array_equal(c["text"][:1300], g["text"][:1300])
+    rows = rc.rows_of(c, rc.run_reference(REF_REFINE, c, str(tmp_path)))
+    assert 2000 <= len(rows) <= 2600
+    gi, _ = small_side([c["text"]])
+    try:
+        check_against_reference(gi, rows)
+    finally:
+        gi.close()
