@@ -39,7 +39,7 @@ EXPORTS = [  # every symbol include/hsa_gpu.h and include/hsa_bwtaln.h declare
     "hsa_index_set_text64_device", "hsa_refine_rows_device64", "hsa_choose_hits_device64",
     "hsa_choose_timing", "hsa_choose_launch_times", "hsa_sam_lines_device64", "hsa_sam_timing", "hsa_splice_lines_device", "hsa_sam_merge_device",
     "hsa_sam_launch_times", "hsa_index_levels", "hsa_reads_device", "hsa_reads_timing",
-    "hsa_reads_launch_times", "hsa_reads_device_opts", "hsa_sam_lines_device64_trim", "hsa_splice_lines_device_trim", "hsa_fasta_scratch_bytes", "hsa_fasta_device", "hsa_bwt_files_scratch_bytes",
+    "hsa_reads_launch_times", "hsa_reads_device_opts", "hsa_sam_lines_device64_trim", "hsa_splice_lines_device_trim", "hsa_splice_lines_device_xa", "hsa_fasta_scratch_bytes", "hsa_fasta_device", "hsa_bwt_files_scratch_bytes",
     "hsa_bwt_files_device", "hsa_fasta_timing", "hsa_fasta_launch_times", "hsa_bwt_files_launch_times",
     "hsa_inflate_bgzf_device", "hsa_bam_reads_device", "hsa_bam_timing", "hsa_bam_launch_times",
 ]
@@ -60,6 +60,8 @@ HSA_SAM_MAX_LINE = 61440
 (HSA_SL_OK, HSA_SL_NONE, HSA_SL_HANDED, HSA_SL_NOPAIR, HSA_SL_MULTI, HSA_SL_REFINE, HSA_SL_POS, HSA_SL_INTRON,
  HSA_SL_INPUT) = range(9)
 SL_ROW_WORDS = 24
+SL_XA_WORDS = 16               # words per extra pair of hsa_splice_lines_device_xa
+HSA_SL_XA_UNUSED = 0xFFFFFFFF
 HSA_SP_MAX_STACKS = 128
 # hsa_reads_device: per-record status, words per record row, the longest read, the bytes of
 # the input per block of the newline passes, the counters
@@ -237,6 +239,14 @@ class SpliceLinesBatch(C.Structure):
                 ("max_len", C.c_int32), ("max_line", C.c_uint32), ("cigar_stride", C.c_uint32), ("pad", C.c_uint32),
                 ("d_rows", C.c_void_p), ("d_cigar", C.c_void_p), ("d_line_off", C.c_void_p), ("d_out", C.c_void_p),
                 ("out_cap", C.c_uint64), ("d_line_stat", C.c_void_p), ("d_counters", C.c_void_p)]
+
+
+class SpliceXa(C.Structure):
+    """hsa_splice_xa_t (include/hsa_gpu.h): the room for the extra splice pairs of reads with
+    several pairs (their XA:Z entries), the pairs' offsets, rows and merged CIGARs and the
+    list counters out, all device pointers."""
+    _fields_ = [("pair_cap", C.c_uint64), ("d_pair_off", C.c_void_p), ("d_pair_rows", C.c_void_p), ("d_pair_cigar", C.c_void_p),
+                ("d_counters", C.c_void_p)]
 
 
 class SamMergeBatch(C.Structure):
@@ -459,6 +469,8 @@ def lib():
     if hasattr(L, "hsa_sam_lines_device64_trim"):
         L.hsa_sam_lines_device64_trim.argtypes = [vp, C.POINTER(SamBatch64), C.POINTER(SamTrim), vp]
         L.hsa_splice_lines_device_trim.argtypes = [vp, C.POINTER(SpliceLinesBatch), C.POINTER(SamTrim), vp]
+    if hasattr(L, "hsa_splice_lines_device_xa"):
+        L.hsa_splice_lines_device_xa.argtypes = [vp, C.POINTER(SpliceLinesBatch), C.POINTER(SamTrim), C.POINTER(SpliceXa), vp]
     if hasattr(L, "hsa_splice_lines_device"):
         L.hsa_splice_lines_device.argtypes = [vp, C.POINTER(SpliceLinesBatch), vp]
         L.hsa_sam_merge_device.argtypes = [vp, C.POINTER(SamMergeBatch), vp]
@@ -870,15 +882,22 @@ class GpuIndex:
         else:
             check(lib().hsa_sam_lines_device64_trim(getattr(self, "h", None), C.byref(batch), C.byref(trim), stream))
 
-    def splice_lines(self, batch: "SpliceLinesBatch", stream=None, trim: "SamTrim" = None):
+    def splice_lines(self, batch: "SpliceLinesBatch", stream=None, trim: "SamTrim" = None, xa: "SpliceXa" = None):
         """hsa_splice_lines_device: the SAM lines of the spliced reads of a batch from
         splice_device's results (batch.d_rows, d_cigar, d_line_off, d_out, d_line_stat,
         d_counters) on `stream` (a hipStream_t address; None: the index's own); does not
         synchronise.  hsa_amd.chain.splice_lines drives it.  trim: as sam_lines64 takes it
-        (hsa_splice_lines_device_trim)."""
+        (hsa_splice_lines_device_trim).  xa: a SpliceXa, and the call is
+        hsa_splice_lines_device_xa: a read with several splice pairs gets its line with the
+        XA:Z list instead of HSA_SL_MULTI (None: the plain entry points)."""
         if not hasattr(lib(), "hsa_splice_lines_device"):
             raise HsaError("this libhsa_gpu.so has no hsa_splice_lines_device: rebuild it")
-        if trim is None:
+        if xa is not None:
+            if not hasattr(lib(), "hsa_splice_lines_device_xa"):
+                raise HsaError("this libhsa_gpu.so has no hsa_splice_lines_device_xa: rebuild it")
+            check(lib().hsa_splice_lines_device_xa(getattr(self, "h", None), C.byref(batch), C.byref(trim) if trim is not None else None,
+                                                   C.byref(xa), stream))
+        elif trim is None:
             check(lib().hsa_splice_lines_device(getattr(self, "h", None), C.byref(batch), stream))
         else:
             check(lib().hsa_splice_lines_device_trim(getattr(self, "h", None), C.byref(batch), C.byref(trim), stream))

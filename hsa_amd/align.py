@@ -34,13 +34,15 @@ score buckets, ValueError otherwise) every such read goes through hsa_splice_dev
 the batch has it (bwtaln.c:331 wrote that read's own through the caller's block).  A result
 that is not two records of type BWA_TYPE_SPLICING is appended to the read's hit list on the
 device and is chosen, refined and printed like any other (its draws are made in read
-order); a spliced result is paired, refined and printed by hsa_splice_lines_device
-(chain.splice_lines: XT:A:S, CIGAR with an N), and the two writers' lines are merged in
-read order.  Then every line the reference prints is printed, except for reads the device
+order); a spliced result is paired, refined and printed by hsa_splice_lines_device_xa
+(chain.splice_lines: XT:A:S, CIGAR with an N, and for a read whose segments combine into
+several pairs at the shortest distance the others as an XA:Z list in the reference's format
+for them, bwtse.c:782-797; `spliced_xa` such reads, `spliced_xa_entries` entries), and the two
+writers' lines are merged in read order.  Then every line the reference prints is printed, except for reads the device
 refuses, each of which gets no line (exact or nothing), counts towards no_line and goes to
 --unaligned: `handed_back` (hsa_splice_device's status > 0: there is no host
-bwt_splice_match here), `spliced_multi` (more than one pair: the reference's XA format for
-them is not built), `spliced_refused` (a segment's alignment not answered, a position in
+bwt_splice_match here), `spliced_multi` (several pairs that found no room: 0, since
+chain.splice_lines runs again with the room the device asks for), `spliced_refused` (a segment's alignment not answered, a position in
 no chromosome block, an N length that is not positive, a line past the bound).  After a
 handed-back read that the reference would have printed as U / R the generator state is no
 longer the reference's, and R reads after it may choose differently; the committed
@@ -521,8 +523,10 @@ def _splice_hits(t, s, first, cnt, stats):
 
 
 def _splice_lines(gi, b, s, first, cnt, chrs, has_qual, opt, stats):
-    """hsa_splice_lines_device over jobs [first, first + cnt): (its output tensors, the bytes
-    of its text, line_stat on the host, the names of the reads it refused)."""
+    """hsa_splice_lines_device_xa over jobs [first, first + cnt): (its output tensors, the bytes
+    of its text, line_stat on the host, the names of the reads it refused).  The text's room
+    allows for the lists of the extra pairs the first run serves (chain.xa_room);
+    chain.splice_lines runs again with what the counters ask for."""
     import torch
     from ._lib import HSA_SL_NONE, HSA_SL_NOPAIR, HSA_SL_OK
     strings = dict(names=b["names"], name_off=b["name_off"][first:], chrs=chrs["chrs"], chr_off=chrs["chr_off"])
@@ -531,17 +535,21 @@ def _splice_lines(gi, b, s, first, cnt, chrs, has_qual, opt, stats):
     noff = b["name_off"][first:first + cnt + 1].cpu().numpy().view(np.uint64)
     max_name = int(np.diff(noff.astype(np.int64)).max()) if cnt else 0
     stride = 33                                             # two segments' ops and the N
-    max_line = max(1, sam.line_bound(max_name, b["max_full"], chrs["max_chr"], stride, 0, 0, "full_len" in b, b.get("bc_len", 0)))
+    # (a list has at most 49 entries, each a chromosome, a position and a merged CIGAR)
+    max_line = max(1, sam.line_bound(max_name, b["max_full"], chrs["max_chr"], stride, 0, 49, "full_len" in b, b.get("bc_len", 0)))
     ks = first - s["sp_first"]
     n_two = int((s["res"][ks * SP_RES_WORDS:(ks + cnt) * SP_RES_WORDS].view(cnt, SP_RES_WORDS)[:, 1] == 2).sum())
     cap = n_two * (max_name + 2 * b["max_full"] + chrs["max_chr"] + b.get("bc_len", 0) + 200) + 64
+    cap += chain.xa_room(cnt) * (chrs["max_chr"] + 64)      # the lists of the extra pairs the first run has room for
     o, ctr = chain.splice_lines(gi, b, s, first, cnt, strings, chrs["n"], max_line, cap, cigar_stride=stride,
                                 max_top2=opt["max_top2"], comp_read=bool(opt["mode"] & MODE_COMPREAD))
     stat = o["stat"].cpu().numpy().view(np.uint32)[:cnt]
     stats["lines"] += int(ctr[2])
     stats["spliced"] += int(ctr[2])
     stats["handed_back"] += int(ctr[3])
-    stats["spliced_multi"] += int(ctr[4])
+    stats["spliced_multi"] += int(ctr[4])                    # (none once the extra pairs had room)
+    stats["spliced_xa"] += int(o["xa"][2])
+    stats["spliced_xa_entries"] += int(o["xa"][3])
     stats["spliced_refused"] += int(ctr[5])
     stats["spliced_no_pair"] += int(ctr[6])
     names = b["names"]
@@ -707,7 +715,7 @@ def align_fastq(gi, chr_names, data_or_path, opts, out, batch_reads=BATCH_READS,
                                 refused=0, batches=0, device_records=0, host_records=0, filtered=0, trimmed_bases=0, total_bases=0)
     if splice:
         stats.update(spliced_sent=0, spliced=0, spliced_unspliced=0, spliced_no_pair=0, handed_back=0, spliced_multi=0,
-                     spliced_refused=0)
+                     spliced_refused=0, spliced_xa=0, spliced_xa_entries=0)
         stats["refused_names"] = []
     pos, state, window = 0, int(rng_state), max(4 << 20, 1024 * int(batch_reads))
     if is_bam:

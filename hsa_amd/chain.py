@@ -33,9 +33,9 @@ from __future__ import annotations
 import numpy as np
 
 from . import reads
-from ._lib import (ALN64_WORDS, HSA_RF_MAX_LEN, HSA_RF_MD, JOB_DTYPE, RF_ROW_WORDS, SL_ROW_WORDS, SP_RES_WORDS, ChooseBatch64,
+from ._lib import (ALN64_WORDS, HSA_RF_MAX_LEN, HSA_RF_MD, JOB_DTYPE, RF_ROW_WORDS, SL_ROW_WORDS, SL_XA_WORDS, SP_RES_WORDS, ChooseBatch64,
                    DeviceBatch, HitPosBatch64, HsaError, RefineBatch64, SamBatch64, SamMergeBatch, SamTrim, SpliceBatch,
-                   SpliceLinesBatch,
+                   SpliceLinesBatch, SpliceXa,
                    anchor_regime, ext_regime, regime_of)
 
 N_MULTI = 3                      # bwtaln.c:514
@@ -275,17 +275,45 @@ def splice_lines_batch(b, s, first, n, strings, n_chr, max_line, out_cap, cigar_
     return lb, o
 
 
+def splice_xa_batch(n, room, cigar_stride=33):
+    """(SpliceXa, its output tensors pair_off, pair_rows, pair_cigar, xa_ctr) for a splice-lines
+    batch of n jobs with room for `room` extra splice pairs (the XA:Z entries of reads with
+    several pairs)."""
+    o = dict(pair_off=_new(n + 1, "int64"), pair_rows=_new(max(room, 1) * SL_XA_WORDS, "int32"),
+             pair_cigar=_new(max(room, 1) * max(cigar_stride, 1), "int32"), xa_ctr=_new(8, "int64"), pair_cap=room)
+    xa = SpliceXa(pair_cap=room, d_pair_off=o["pair_off"].data_ptr(), d_pair_rows=o["pair_rows"].data_ptr(),
+                  d_pair_cigar=o["pair_cigar"].data_ptr(), d_counters=o["xa_ctr"].data_ptr())
+    return xa, o
+
+
+def xa_room(n):
+    """The extra pairs a first run of splice_lines has room for: every slot is two more rows
+    for the refinement, used or not, so a sixteenth of the reads and 64."""
+    return n // 16 + 64
+
+
 def splice_lines(gi, b, s, first, n, strings, n_chr, max_line, out_cap, **kw):
-    """hsa_splice_lines_device over jobs [first, first + n) with room for out_cap bytes, run a
-    second time with counters[0] bytes of room when the first reports wanted > written: (the
-    output tensors, the counters as 8 u64 on the host)."""
-    for _ in range(2):
+    """hsa_splice_lines_device_xa over jobs [first, first + n) with room for out_cap bytes and
+    xa_room(n) extra splice pairs, run again with the room the counters ask for while a run
+    reports wanted > served (pairs: xa_ctr[0] > the room; bytes: ctr[0] > ctr[1]): (the output
+    tensors, those of splice_xa_batch among them and the list counters as o["xa"], 8 u64 on the
+    host; the counters as 8 u64 on the host)."""
+    room = xa_room(n)
+    coff = strings["chr_off"][:n_chr + 1].cpu().numpy().view(np.uint64).astype(np.int64)
+    entry_chr = int(np.diff(coff).max()) if n_chr else 0
+    for _ in range(4):
         lb, o = splice_lines_batch(b, s, first, n, strings, n_chr, max_line, out_cap, **kw)
-        _call(gi.splice_lines, lb, trim=sam_trim(trim_views(b, first)))
+        xa, ox = splice_xa_batch(n, room, o["cigar_stride"])
+        _call(gi.splice_lines, lb, trim=sam_trim(trim_views(b, first)), xa=xa)
         ctr = o["ctr"].cpu().numpy().view(np.uint64)
-        if int(ctr[0]) <= int(ctr[1]):
+        xc = ox["xa_ctr"].cpu().numpy().view(np.uint64)
+        o.update(ox, xa=xc)
+        if int(xc[0]) <= room and int(ctr[0]) <= int(ctr[1]):
             break
-        out_cap = int(ctr[0])
+        # a run short of room counted no byte of the lists it left out: allow for them, so that
+        # the next run is the last (an entry: the chromosome, ",+", a position, some ten ops)
+        more = max(0, int(xc[0]) - room) * (entry_chr + 64)
+        room, out_cap = max(room, int(xc[0])), max(out_cap, int(ctr[0]) + more)
     return o, ctr
 
 

@@ -17,8 +17,7 @@ the text hsa_splice_lines_device (hsa_amd/csrc/hsa_splice_rows.hip) is tested ag
 
 A trimmed read (bwa aln -q) and a barcode (-B) reach both: SEQ and QUAL over the whole read,
 bwa_correct_trimmed on the line's own CIGAR, BC:Z and XC:i behind QUAL.  Not printed: the RG
-tag (no read group reaches the 64-bit path) and the XA list of a spliced read with more than
-one pair."""
+tag (no read group reaches the 64-bit path)."""
 from __future__ import annotations
 
 import numpy as np
@@ -115,7 +114,7 @@ CIGAR_OPS = "MIDNSHP=X"      # bwtse.c:713
 
 
 def spliced_line(name, seq_codes, qual, chr_name, ori_pos, cigar, strand, c1, c2, n_mm, max_top2=30, flag=0,
-                 comp_read=True, clip_len=None, bc=None) -> str:
+                 comp_read=True, clip_len=None, bc=None, xa=None) -> str:
     """The line of a spliced read (bwa_print_sam1 for type BWA_TYPE_SPLICING, bwtse.c:677-799),
     without the newline.
 
@@ -125,7 +124,11 @@ def spliced_line(name, seq_codes, qual, chr_name, ori_pos, cigar, strand, c1, c2
     (bwtse.c:310-315); n_mm: mm of segment 0 plus mm of segment 1 (:594).  mapQ is 0 (the
     value of :345 is dropped), NM is 0 (nm is never computed for these reads), XO and XG are
     0 (gap is never set), and there is no MD.  clip_len, bc: as sam_line takes them (the
-    segments lie in the trimmed read)."""
+    segments lie in the trimmed read).  xa: the read's further splice pairs
+    (hsa_amd.splice.multi_entries: chromosome name, strand, 1-based position, merged CIGAR as
+    (op, length) pairs), printed as the reference does (:782-797): "<chr>,<+|-><position>"
+    and the CIGAR's ops from "MIDNS" directly behind it, no edit count, no ';', the entries
+    abutting; bwa_correct_trimmed does not touch these CIGARs."""
     seq_codes = np.asarray(seq_codes, np.uint8)
     if strand:
         flag |= SAM_FSR
@@ -143,6 +146,9 @@ def spliced_line(name, seq_codes, qual, chr_name, ori_pos, cigar, strand, c1, c2
     if c1 <= max_top2:
         out.append(f"X1:i:{int(c2)}")
     out += [f"XM:i:{int(n_mm)}", "XO:i:0", "XG:i:0"]
+    if xa:
+        out.append("XA:Z:" + "".join(f"{c},{'-' if st else '+'}{int(pos)}" + "".join(f"{int(l)}{'MIDNS'[op]}" for op, l in cg)
+                                     for c, st, pos, cg in xa))
     return "\t".join(out)
 
 

@@ -234,6 +234,17 @@ def merge_cigar(cigar0, ori0: int, end0: int, cigar1, ori1: int):
     return list(cigar0) + [(3, ori1 - ori0 - end0)] + list(cigar1)
 
 
+def multi_entries(pairs):
+    """What bwa_refine_gapped leaves in multi[0 .. n_multi - 2] of a spliced read with n_multi
+    splice pairs (bwtse.c:603-618), the entries of its XA list.  pairs: per pair of
+    pair_segments, in its order and pair 0 (the read's own alignment) included,
+    (seq_id, strand, cigar0, ori0, end0, cigar1, ori1) after refine_gapped_core (the arguments
+    of merge_cigar).  Pair i >= 1 becomes entry i - 1: a copy of the pair's first segment
+    (seq_id, strand, ori_pos) with the merged CIGAR.  Returns (seq_id, strand, ori_pos,
+    cigar) per entry."""
+    return [(seq_id, strand, ori0, merge_cigar(c0, ori0, end0, c1, ori1)) for seq_id, strand, c0, ori0, end0, c1, ori1 in pairs[1:]]
+
+
 def run_seed_calls(gi, batch, n_stacks: int):
     """All seed calls of `batch` in one hsa_match_gap_batch pass.
     Returns (n_aln, hit_off, hits, widths after, stats)."""

@@ -880,7 +880,8 @@ int hsa_sam_launch_times(hsa_index_t *ix, float *ms);
  * result (not sent to the splice path, or n_aln is not 2 records of type 4); HSA_SL_HANDED
  * hsa_splice_device's status is > 0; HSA_SL_NOPAIR no pair of rows combines (the reference
  * sets BWA_TYPE_NO_MATCH, :339-342); HSA_SL_MULTI more than one pair (the reference prints
- * the others as XA in a format of its own, :596-618: not built); HSA_SL_REFINE a segment's
+ * the others as XA in a format of its own, :596-618: hsa_splice_lines_device_xa below
+ * prints them; these two calls refuse the read); HSA_SL_REFINE a segment's
  * alignment was not answered; HSA_SL_POS a paired row lies in no chromosome block, or the
  * two on different chromosomes; HSA_SL_INTRON the N length is not positive; HSA_SL_INPUT a
  * record field, string offset or CIGAR outside what the layout holds, or a line past
@@ -927,6 +928,56 @@ typedef struct {
 int hsa_splice_lines_device(hsa_index_t *ix, const hsa_splice_lines_batch_t *b, void *stream);
 /* ... with trimmed reads and barcodes (hsa_sam_trim_t above; the segments lie in hsa_job_t.len) */
 int hsa_splice_lines_device_trim(hsa_index_t *ix, const hsa_splice_lines_batch_t *b, const hsa_sam_trim_t *trim, void *stream);
+/* ... and with the XA:Z lists of reads whose segments combine into several pairs at the
+ * shortest distance (bwtse.c:596-618 and :782-797).  The two calls above give such a read
+ * HSA_SL_MULTI and no line, and keep doing so; through this one it gets the reference's whole
+ * line.  bwt_combine_segment_splice keeps the pair at the sorted index where the shortest
+ * distance was last lowered and every later adjacent (segment 0, segment 1) pair on one
+ * chromosome at that distance, in sorted order, at most 50.  Pair 0 is the read's own
+ * alignment as before; pair i >= 1 ("extra pair" below) is XA entry i - 1: both segments go
+ * through refine_gapped_core, and the entry is "<chr>,<+|-><segment 0's position>" followed
+ * directly by the ops of (segment 0's CIGAR, N of ori_pos1 - ori_pos0 - end0, segment 1's
+ * CIGAR) from "MIDNS" -- no comma, no edit count, no ';', the entries abut.
+ * bwa_correct_trimmed does not touch these CIGARs.
+ *
+ * The number of extra pairs is known only on the device and the call makes no host round
+ * trip, so the caller states the room (pair_cap extra pairs for the whole batch, as out_cap
+ * states the text's).  Reads are served in read order while their pairs fit; a read whose
+ * pairs do not fit gets HSA_SL_MULTI and no line.  d_counters (>= 8 u64, zeroed by the call):
+ * [0] extra pairs wanted, [1] extra pairs served, [2] reads printed with a list, [3] entries
+ * printed.  [0] > pair_cap: run again with [0] pairs of room; then no read is HSA_SL_MULTI.
+ * An extra pair that fails refuses the whole read with that pair's status (a row in no
+ * chromosome block HSA_SL_POS, a segment not answered HSA_SL_REFINE, an N length that is not
+ * positive HSA_SL_INTRON, a CIGAR past cigar_stride HSA_SL_INPUT): exact or nothing.
+ *
+ * Outputs: d_pair_off (n_jobs + 1: read j's extra pairs are [d_pair_off[j], d_pair_off[j +
+ * 1]), whether they were served or not), d_pair_rows (HSA_SL_XA_WORDS u32 per served extra
+ * pair: status, read, bytes of its entry, the entry's offset in the read's XA text, merged
+ * n_cigar, N length, chrID, then segment 0's 1-based position, text position and end and
+ * segment 1's 1-based position and text position (after refine_gapped_core's adjustments
+ * when the status is HSA_SL_OK), strand, the two segments' n_cigar, segment 0's position as
+ * paired), d_pair_cigar (the batch's cigar_stride words per extra pair).  d_rows words 22
+ * and 23 of a read hold its served extra pairs and the bytes of its XA text.  With no read
+ * of several pairs the text, the rows and the eight counters are those of
+ * hsa_splice_lines_device_trim.  `trim` may be NULL.
+ *
+ * Launches: k_sl_pair also counts each read's extra pairs, a scan gives d_pair_off, k_sl_room
+ * blanks the extra refine rows, k_sl_fill (one wavefront per read with extra pairs, the
+ * others leave at once; the lanes test the sorted rows and number the kept pairs by ballot
+ * and prefix popcount) fills them behind the 2 n_jobs rows of the first pairs, one refine
+ * launch serves all rows, k_sl_xlen (one lane per extra pair) merges and measures the entries,
+ * and k_sl_write's lanes format a read's entries side by side. */
+#define HSA_SL_XA_WORDS 16
+#define HSA_SL_XA_UNUSED 0xFFFFFFFFu   /* d_pair_rows word 0 of a slot no pair was served in */
+typedef struct {
+    uint64_t pair_cap;               /* room: extra pairs of the whole batch */
+    uint64_t *d_pair_off;            /* n_jobs + 1 */
+    uint32_t *d_pair_rows;           /* HSA_SL_XA_WORDS u32 per extra pair (pair_cap of them) */
+    uint32_t *d_pair_cigar;          /* cigar_stride u32 per extra pair */
+    uint64_t *d_counters;            /* >= 8 u64 */
+} hsa_splice_xa_t;
+int hsa_splice_lines_device_xa(hsa_index_t *ix, const hsa_splice_lines_batch_t *b, const hsa_sam_trim_t *trim,
+                               const hsa_splice_xa_t *xa, void *stream);
 /* The lines of two writers over the same reads (hsa_sam_lines_device64's and
  * hsa_splice_lines_device's: a read has a line from at most one of them) as one text in read
  * order: d_line_off[j] is the sum of the two inputs' offsets, and read j's bytes are writer
