@@ -42,6 +42,7 @@ EXPORTS = [  # every symbol include/hsa_gpu.h and include/hsa_bwtaln.h declare
     "hsa_reads_launch_times", "hsa_reads_device_opts", "hsa_sam_lines_device64_trim", "hsa_splice_lines_device_trim", "hsa_splice_lines_device_xa", "hsa_fasta_scratch_bytes", "hsa_fasta_device", "hsa_bwt_files_scratch_bytes",
     "hsa_bwt_files_device", "hsa_fasta_timing", "hsa_fasta_launch_times", "hsa_bwt_files_launch_times",
     "hsa_inflate_bgzf_device", "hsa_bam_reads_device", "hsa_bam_timing", "hsa_bam_launch_times",
+    "hsa_junction_rows_device", "hsa_junction_reduce_device", "hsa_junction_text_device",
 ]
 SP_RES_WORDS = 20  # hsa_splice_match_batch's per-read answer (include/hsa_gpu.h)
 ALN64_WORDS = 14   # hsa_aln64_t (include/hsa_gpu.h)
@@ -62,6 +63,9 @@ HSA_SAM_MAX_LINE = 61440
 SL_ROW_WORDS = 24
 SL_XA_WORDS = 16               # words per extra pair of hsa_splice_lines_device_xa
 HSA_SL_XA_UNUSED = 0xFFFFFFFF
+# the junction table's row buffers: words per row (chrID, first base, last base, lines without an XA list, lines with
+# one, overhang, motif, 0)
+JN_ROW_WORDS = 8
 HSA_SP_MAX_STACKS = 128
 # hsa_reads_device: per-record status, words per record row, the longest read, the bytes of
 # the input per block of the newline passes, the counters
@@ -247,6 +251,27 @@ class SpliceXa(C.Structure):
     list counters out, all device pointers."""
     _fields_ = [("pair_cap", C.c_uint64), ("d_pair_off", C.c_void_p), ("d_pair_rows", C.c_void_p), ("d_pair_cigar", C.c_void_p),
                 ("d_counters", C.c_void_p)]
+
+
+class JunctionRowsBatch(C.Structure):
+    """hsa_junction_rows_batch_t (include/hsa_gpu.h): one lines call's rows, CIGARs and statuses
+    in; junction rows appended to a row buffer, all device pointers."""
+    _fields_ = [("n_jobs", C.c_int), ("cigar_stride", C.c_uint32), ("d_rows", C.c_void_p), ("d_cigar", C.c_void_p),
+                ("d_line_stat", C.c_void_p), ("d_jrows", C.c_void_p), ("n_have", C.c_uint64), ("row_cap", C.c_uint64),
+                ("d_counters", C.c_void_p)]
+
+
+class JunctionReduceBatch(C.Structure):
+    """hsa_junction_reduce_batch_t (include/hsa_gpu.h): a row buffer sorted and merged in place."""
+    _fields_ = [("d_jrows", C.c_void_p), ("n_rows", C.c_uint64), ("d_counters", C.c_void_p)]
+
+
+class JunctionTextBatch(C.Structure):
+    """hsa_junction_text_batch_t (include/hsa_gpu.h): a reduced table and the chromosome names
+    in; the table's text and its per-row offsets out, all device pointers."""
+    _fields_ = [("d_jrows", C.c_void_p), ("n_rows", C.c_uint64), ("d_chr_names", C.c_void_p), ("d_chr_off", C.c_void_p),
+                ("n_chr", C.c_uint32), ("pad", C.c_uint32), ("d_line_off", C.c_void_p), ("d_out", C.c_void_p),
+                ("out_cap", C.c_uint64), ("d_counters", C.c_void_p)]
 
 
 class SamMergeBatch(C.Structure):
@@ -476,6 +501,10 @@ def lib():
         L.hsa_sam_merge_device.argtypes = [vp, C.POINTER(SamMergeBatch), vp]
         L.hsa_sam_timing.restype = None
         L.hsa_sam_launch_times.argtypes = [vp, f32]
+    if hasattr(L, "hsa_junction_rows_device"):      # (older A/B builds lack the junction table)
+        L.hsa_junction_rows_device.argtypes = [vp, C.POINTER(JunctionRowsBatch), vp]
+        L.hsa_junction_reduce_device.argtypes = [vp, C.POINTER(JunctionReduceBatch), vp]
+        L.hsa_junction_text_device.argtypes = [vp, C.POINTER(JunctionTextBatch), vp]
     if hasattr(L, "hsa_reads_device"):              # (older A/B builds lack the FASTQ loader)
         L.hsa_reads_device.argtypes = [vp, C.POINTER(ReadsBatch), vp]
         if hasattr(L, "hsa_reads_device_opts"):
@@ -901,6 +930,26 @@ class GpuIndex:
             check(lib().hsa_splice_lines_device(getattr(self, "h", None), C.byref(batch), stream))
         else:
             check(lib().hsa_splice_lines_device_trim(getattr(self, "h", None), C.byref(batch), C.byref(trim), stream))
+
+    def _junction_call(self, name, batch, stream):
+        if not hasattr(lib(), name):
+            raise HsaError(f"this libhsa_gpu.so has no {name}: rebuild it")
+        check(getattr(lib(), name)(getattr(self, "h", None), C.byref(batch), stream))
+
+    def junction_rows(self, batch: "JunctionRowsBatch", stream=None):
+        """hsa_junction_rows_device: one junction row per printed spliced read of a lines call,
+        appended to a row buffer.  The call does not synchronise; hsa_amd.chain.junction_rows
+        drives it."""
+        self._junction_call("hsa_junction_rows_device", batch, stream)
+
+    def junction_reduce(self, batch: "JunctionReduceBatch", stream=None):
+        """hsa_junction_reduce_device: a row buffer sorted, equal introns merged, the motifs
+        read from the text, in place (hsa_amd.chain.junction_reduce)."""
+        self._junction_call("hsa_junction_reduce_device", batch, stream)
+
+    def junction_text(self, batch: "JunctionTextBatch", stream=None):
+        """hsa_junction_text_device: the text of a reduced table (hsa_amd.chain.junction_text)."""
+        self._junction_call("hsa_junction_text_device", batch, stream)
 
     def sam_merge(self, batch: "SamMergeBatch", stream=None):
         """hsa_sam_merge_device: the lines of sam_lines64 and of splice_lines over the same

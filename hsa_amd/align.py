@@ -79,6 +79,14 @@ single-anchor walk) and bam_truncated: a truncated or inconsistent record ends t
 there, the reads before it are aligned, and main returns 1.  Without the BAM bit nothing
 changes, the keys of the statistics included.
 
+--junctions FILE (with --splice; align_fastq's junctions=<binary file object>) writes the run's
+splice junction table after the last batch: one row per distinct intron of the printed XT:A:S
+lines in the nine columns of STAR's SJ.out.tab, made on the device from what
+hsa_splice_lines_device_xa leaves there (hsa_amd.junctions states the table and restates it on
+the host from the SAM text; hsa_junctions.hip).  The statistics gain junction_rows (rows fed:
+the spliced lines) and junctions (distinct introns).  Without the option the text, the
+statistics' keys and the calls made are the same as before.
+
 Not built: colour space (-c): refused.  -t is accepted and
 ignored.  A read the choice counts as a zero-draw read (probability 2^-48 per read) stops the
 run with an error."""
@@ -134,7 +142,8 @@ def _atof(s: str) -> float:
 
 def parse_options(args, reader_options=False, bam_options=False):
     """bwa_aln's option switch (bwtaln.c:539-575) over `args`: (the option dict, the
-    positional arguments, dict(header, unaligned, out)).  Options of what is not built raise
+    positional arguments, dict(header, unaligned, out), with the keys splice and junctions only
+    when --splice and --junctions FILE are given).  Options of what is not built raise
     ValueError.  reader_options: take the reader's options as the switch sets them (:558,
     :566-568): -q INT (trim_qual), -B INT (mode |= n << 24), -I (MODE_IL13), -Y (MODE_CFY); a
     barcode over BWA_MAX_BCLEN (the reference then reads nothing) and a trim_qual over
@@ -146,7 +155,7 @@ def parse_options(args, reader_options=False, bam_options=False):
     o = default_opts()
     extra = dict(header=False, unaligned=None, out=None)
     opte = -1
-    optlist, rest = getopt.gnu_getopt(list(args), OPTSTRING, ["header", "unaligned=", "splice"])
+    optlist, rest = getopt.gnu_getopt(list(args), OPTSTRING, ["header", "unaligned=", "splice", "junctions="])
     plain = {"-o": "max_gapo", "-M": "s_mm", "-O": "s_gapo", "-E": "s_gape", "-d": "max_del_occ", "-i": "indel_end_skip",
              "-l": "seed_len", "-k": "max_seed_diff", "-m": "max_entries", "-t": "n_threads", "-R": "max_top2"}
     for k, v in optlist:
@@ -185,6 +194,8 @@ def parse_options(args, reader_options=False, bam_options=False):
             extra["unaligned"] = v
         elif k == "--splice":
             extra["splice"] = True                          # (the key is there only when the option is)
+        elif k == "--junctions":
+            extra["junctions"] = v                          # (likewise)
         else:
             raise ValueError(f"option {k} is not built" + (" (colour space)" if bam_options else " (BAM input, colour space)" if reader_options else
                                                            " (barcodes, Casava filter, Illumina-1.3 qualities, BAM, colour space)"))
@@ -558,9 +569,10 @@ def _splice_lines(gi, b, s, first, cnt, chrs, has_qual, opt, stats):
     return o, int(ctr[1]), stat, refused
 
 
-def _run_batch(gi, chr_names, b, opt, out, state, stats, splice=False):
+def _run_batch(gi, chr_names, b, opt, out, state, stats, splice=False, junctions=None):
     """Steps 2 to 5 for a merged batch; returns the generator's state and, per job, whether
-    it got a line."""
+    it got a line.  junctions: a junctions.Accumulator that takes the rows of every
+    splice-lines call, or None."""
     import torch
     n = b["n_jobs"]
     local, n_stacks, rg_b = chain.local_regime(opt, b["max_all"])      # bwtaln.c:254, :273-276
@@ -651,6 +663,8 @@ def _run_batch(gi, chr_names, b, opt, out, state, stats, splice=False):
         if s is not None:
             # the two writers' lines in read order (hsa_sam_merge_device), then one copy to the host
             o2, written2, stat2, refused = _splice_lines(gi, b, s, first, cnt, chrs, bool(b["has_qual"][first]), opt, stats)
+            if junctions is not None:
+                junctions.add(o2, cnt)
             mo, mc = chain.sam_merge(gi, cnt, (text, int(ctr[1]), off), (o2["out"], written2, o2["line_off"]))
             assert int(mc[0]) == int(mc[1]) == int(ctr[1]) + written2
             out.write(mo["out"][:int(mc[1])].cpu().numpy().tobytes())
@@ -675,16 +689,22 @@ def _read_input(data_or_path) -> bytes:
 
 
 def align_fastq(gi, chr_names, data_or_path, opts, out, batch_reads=BATCH_READS, rng_state=HSA_DRAND48_SEED0, unaligned=None,
-                splice=False):
+                splice=False, junctions=None, junction_threshold=None):
     """FASTQ (bytes, or a path; gzip is read through Python's gzip), or with the BAM bit of
     opts["mode"] a BAM file (bytes or a path; the module docstring), to SAM text written to
     `out` (a binary file object), as the module docstring states it.  opts: an option dict
     (default_opts / parse_options), not modified.  unaligned: a binary file object for the
     reads without a line.  splice: send the reads without a main-search hit through the splice
-    path and print its lines too (the module docstring's contract).  Returns (the drand48 state
-    after the last read, statistics)."""
+    path and print its lines too (the module docstring's contract).  junctions: a binary file
+    object that receives the run's splice junction table after the last batch (hsa_amd.junctions;
+    with splice only, ValueError otherwise; junction_threshold: the rows after which the device
+    row buffer is compacted, junctions.Accumulator's default when None); the statistics then
+    gain junction_rows and junctions.  Returns (the drand48 state after the last read,
+    statistics)."""
     import collections
     import torch
+    if junctions is not None and not splice:
+        raise ValueError("--junctions goes with --splice: the table is made of the spliced reads' lines")
     opt = dict(opts)
     opt.setdefault("trim_qual", 0)
     is_bam = bool(opt["mode"] & MODE_BAM)
@@ -717,6 +737,10 @@ def align_fastq(gi, chr_names, data_or_path, opts, out, batch_reads=BATCH_READS,
         stats.update(spliced_sent=0, spliced=0, spliced_unspliced=0, spliced_no_pair=0, handed_back=0, spliced_multi=0,
                      spliced_refused=0, spliced_xa=0, spliced_xa_entries=0)
         stats["refused_names"] = []
+    acc = None
+    if junctions is not None:
+        from .junctions import Accumulator
+        acc = Accumulator(gi, chr_names, **({} if junction_threshold is None else dict(threshold=junction_threshold)))
     pos, state, window = 0, int(rng_state), max(4 << 20, 1024 * int(batch_reads))
     if is_bam:
         stats.update({"inflate_" + k: v for k, v in inflate.items()})
@@ -739,7 +763,7 @@ def align_fastq(gi, chr_names, data_or_path, opts, out, batch_reads=BATCH_READS,
         stats.update(b["reader"])                           # (a Counter: adds)
         stats["device_records"] += sum(s["t"]["n_loaded"] for s in segs if s["kind"] == "dev")
         stats["host_records"] += sum(len(s["p"]["names"]) for s in segs if s["kind"] == "host")
-        state, has_line = _run_batch(gi, chr_names, b, opt, out, state, stats, splice=splice)
+        state, has_line = _run_batch(gi, chr_names, b, opt, out, state, stats, splice=splice, junctions=acc)
         if unaligned is not None:
             p = bam.parse_host(data[start:pos], len(rec), which=src["which"], trim_qual=opt["trim_qual"]) if is_bam else \
                 reads.parse_host(data[start:pos], len(rec), **rd)
@@ -753,6 +777,9 @@ def align_fastq(gi, chr_names, data_or_path, opts, out, batch_reads=BATCH_READS,
                 else:
                     unaligned.write(b"@" + p["names"][r] + b"\n" + seq + b"\n+\n" + qual + b"\n")
     stats["no_line"] = stats["reads"] - stats["lines"]
+    if acc is not None:
+        junctions.write(acc.finish())                       # (an empty table for a run without a spliced line)
+        stats["junction_rows"], stats["junctions"] = acc.fed, acc.distinct
     return state, dict(stats)
 
 
@@ -770,16 +797,21 @@ def main(argv=None) -> int:
         print(f"hsa_amd.align: {e}", file=sys.stderr)
         return 1
     if len(rest) < 2:
-        print("usage: python -m hsa_amd.align [bwa-aln options] [--header] [--unaligned FILE] [--splice] [-f OUT] <prefix> <in.fq | -b in.bam>",
+        print("usage: python -m hsa_amd.align [bwa-aln options] [--header] [--unaligned FILE] [--splice [--junctions FILE]] [-f OUT] "
+              "<prefix> <in.fq | -b in.bam>",
               file=sys.stderr)
+        return 1
+    if "junctions" in extra and not extra.get("splice"):
+        print("hsa_amd.align: --junctions goes with --splice", file=sys.stderr)
         return 1
     gi, chrs = open_index64(rest[0])
     out = open(extra["out"], "wb") if extra["out"] else sys.stdout.buffer
     un = open(extra["unaligned"], "wb") if extra["unaligned"] else None
+    jn = open(extra["junctions"], "wb") if "junctions" in extra else None
     try:
         if extra["header"]:
             out.write(sam_header(rest[0]))
-        _, stats = align_fastq(gi, chrs, rest[1], opts, out, unaligned=un, splice=extra.get("splice", False))
+        _, stats = align_fastq(gi, chrs, rest[1], opts, out, unaligned=un, splice=extra.get("splice", False), junctions=jn)
         out.flush()
     except bam.BamError as e:                               # a file that is not BAM
         print(f"hsa_amd.align: {e}", file=sys.stderr)
@@ -787,6 +819,8 @@ def main(argv=None) -> int:
     finally:
         if un:
             un.close()
+        if jn:
+            jn.close()
         if extra["out"]:
             out.close()
         gi.close()

@@ -22,7 +22,10 @@ outputs added, so the dict of the last stage holds the whole chain:
   refine          rows, rpos, cigar, md, ctr, cigar_stride, md_stride;
   splice          res (HSA_SP_RES_WORDS words per job), sp_ctr, sp_first (the batch's job
                   the arrays start at), sp_flags and sp_n_aln (what the call was given);
-  splice lines    line_off, stat, ctr, out, rows (SL_ROW_WORDS words per job), cigar.
+  splice lines    line_off, stat, ctr, out, rows (SL_ROW_WORDS words per job), cigar;
+  junction table  a row buffer of its own (JN_ROW_WORDS words per row) that the three junction
+                  stages append to, reduce in place and print (hsa_amd.junctions.Accumulator
+                  owns it over the batches of a run).
 
 Every stage is a builder and a driver.  The builder (`*_batch`) allocates the outputs and
 returns the filled ctypes struct of _lib with the tensors; a probe builds once and times many
@@ -34,7 +37,8 @@ import numpy as np
 
 from . import reads
 from ._lib import (ALN64_WORDS, HSA_RF_MAX_LEN, HSA_RF_MD, JOB_DTYPE, RF_ROW_WORDS, SL_ROW_WORDS, SL_XA_WORDS, SP_RES_WORDS, ChooseBatch64,
-                   DeviceBatch, HitPosBatch64, HsaError, RefineBatch64, SamBatch64, SamMergeBatch, SamTrim, SpliceBatch,
+                   DeviceBatch, HitPosBatch64, HsaError, JunctionReduceBatch, JunctionRowsBatch, JunctionTextBatch, RefineBatch64, SamBatch64,
+                   SamMergeBatch, SamTrim, SpliceBatch,
                    SpliceLinesBatch, SpliceXa,
                    anchor_regime, ext_regime, regime_of)
 
@@ -334,6 +338,66 @@ def sam_merge(gi, n, a, b):
     mb, o = sam_merge_batch(n, a, b)
     _call(gi.sam_merge, mb)
     return o, o["ctr"].cpu().numpy().view(np.uint64)
+
+
+# ---------------------------------------------------------------- junction table
+def junction_rows_batch(o, n, jrows, n_have, row_cap):
+    """(JunctionRowsBatch, the counters' tensor) for the n jobs of splice_lines' output tensors
+    o (rows, cigar, stat, cigar_stride) and a row buffer jrows (JN_ROW_WORDS int32 per row,
+    row_cap rows) that holds n_have rows."""
+    ctr = _new(8, "int64")
+    jb = JunctionRowsBatch(n_jobs=n, cigar_stride=int(o["cigar_stride"]), d_rows=o["rows"].data_ptr(), d_cigar=o["cigar"].data_ptr(),
+                           d_line_stat=o["stat"].data_ptr(), d_jrows=jrows.data_ptr(), n_have=int(n_have), row_cap=int(row_cap),
+                           d_counters=ctr.data_ptr())
+    return jb, ctr
+
+
+def junction_rows(gi, o, n, jrows, n_have, row_cap):
+    """hsa_junction_rows_device: the counters as 8 u64 on the host ([0] rows wanted, [1] rows
+    written behind the n_have the buffer held).  hsa_amd.junctions.Accumulator grows the buffer
+    and runs it again when wanted > written."""
+    jb, ctr = junction_rows_batch(o, n, jrows, n_have, row_cap)
+    _call(gi.junction_rows, jb)
+    return ctr.cpu().numpy().view(np.uint64)
+
+
+def junction_reduce_batch(jrows, n_rows):
+    """(JunctionReduceBatch, the counters' tensor) for the first n_rows rows of a row buffer."""
+    ctr = _new(8, "int64")
+    return JunctionReduceBatch(d_jrows=jrows.data_ptr(), n_rows=int(n_rows), d_counters=ctr.data_ptr()), ctr
+
+
+def junction_reduce(gi, jrows, n_rows):
+    """hsa_junction_reduce_device, in place: the counters as 8 u64 on the host ([0] rows in,
+    [1] rows out)."""
+    rb, ctr = junction_reduce_batch(jrows, n_rows)
+    _call(gi.junction_reduce, rb)
+    return ctr.cpu().numpy().view(np.uint64)
+
+
+def junction_text_batch(jrows, n_rows, chrs, chr_off, n_chr, out_cap):
+    """(JunctionTextBatch, the output tensors line_off, out, ctr) for a reduced table of n_rows
+    rows; chrs, chr_off: the chromosome names as the line writers take them."""
+    import torch
+    o = dict(line_off=_new(n_rows + 1, "int64"), out=torch.empty(max(out_cap, 1), dtype=torch.uint8, device="cuda"), ctr=_new(8, "int64"))
+    tb = JunctionTextBatch(d_jrows=jrows.data_ptr(), n_rows=int(n_rows), d_chr_names=chrs.data_ptr(), d_chr_off=chr_off.data_ptr(),
+                           n_chr=n_chr, d_line_off=o["line_off"].data_ptr(), d_out=o["out"].data_ptr(), out_cap=int(out_cap),
+                           d_counters=o["ctr"].data_ptr())
+    return tb, o
+
+
+def junction_text(gi, jrows, n_rows, chrs, chr_off, n_chr, out_cap):
+    """hsa_junction_text_device with room for out_cap bytes, run a second time with counters[0]
+    bytes of room when the first reports wanted > written: (the output tensors, the counters as
+    8 u64 on the host)."""
+    for _ in range(2):
+        tb, o = junction_text_batch(jrows, n_rows, chrs, chr_off, n_chr, out_cap)
+        _call(gi.junction_text, tb)
+        ctr = o["ctr"].cpu().numpy().view(np.uint64)
+        if int(ctr[0]) <= int(ctr[1]):
+            break
+        out_cap = int(ctr[0])
+    return o, ctr
 
 
 # ---------------------------------------------------------------- SAM lines

@@ -996,6 +996,79 @@ typedef struct {
 } hsa_sam_merge_batch_t;
 int hsa_sam_merge_device(hsa_index_t *ix, const hsa_sam_merge_batch_t *b, void *stream);
 
+/* ---- the splice junction table ----
+ * One row per distinct intron of the XT:A:S lines a run prints, with its read support, as text
+ * in the nine tab-separated columns of STAR's SJ.out.tab: chromosome name; first base of the
+ * intron, 1-based (POS plus the M and D lengths before the N); last base (first + N length -
+ * 1); strand from the motif (1 for motifs 1 3 5, 2 for 2 4 6, 0 for 0); motif from the forward
+ * text's two first and two last intron bases (1 GT/AG, 2 CT/AC, 3 GC/AG, 4 CT/GC, 5 AT/AC,
+ * 6 GT/AT, 0 anything else); 0 (no annotation); lines with this intron and no XA:Z list;
+ * lines with it and a list; the maximum over those lines of min(M lengths before the N, M
+ * lengths behind it).  Rows are in (chrID, first base, last base) order, lines end in '\n',
+ * no header.  The reference prints no such table: it is a function of the printed SAM text
+ * and the index's text and block table (hsa_amd.junctions.from_sam restates it from them).
+ * Only a line's own alignment counts; the introns of its XA:Z entries do not (the reference
+ * prints an entry's position and first op length with nothing between them, so the text does
+ * not determine them).
+ *
+ * A row buffer: HSA_JN_ROW_WORDS u32 per row: chrID, first base, last base, lines without a
+ * list, lines with one, overhang, motif (written by the reduction; 0 before), 0.  Rows carry
+ * counts, so a reduced table is a row buffer too.
+ *
+ * The three calls launch on the caller's stream (NULL: the index's own) without
+ * synchronising, keep their scratch on the handle (hsa_index_release_scratch; shared with
+ * hsa_splice_lines_device, so on one stream with it), zero their d_counters (>= 8 u64), write
+ * nothing past a capacity, place no row or byte with an atomic, and give equal arrays when run
+ * twice.  They need an index under 2^32 characters.
+ *
+ * hsa_junction_rows_device appends one row per read whose d_line_stat is HSA_SL_OK, in read
+ * order, behind the n_have rows the buffer holds, from one lines call's d_rows, d_cigar and
+ * d_line_stat (a flag per read, a scan, a write).  d_counters: [0] rows wanted, [1] rows
+ * written (min of [0] and row_cap - n_have); [0] > [1]: grow the buffer and run again.
+ *
+ * hsa_junction_reduce_device sorts the n_rows rows (rocPRIM radix sort over the three key
+ * words) and merges equal introns in place (rocPRIM reduce_by_key: sums of the two counts,
+ * max of the overhang, runs of any length), then reads each distinct intron's motif from the
+ * packed text: each of the four bases' chromosome coordinates maps through the block table
+ * on its own, and a base in no block (inside an N run) makes the motif 0.  Idempotent.
+ * Needs hsa_index_set_sa (the block table, ascending in (chrID, ori) as the .ann file lists
+ * it) and hsa_index_set_text.  d_counters: [0] rows in, [1] rows out.
+ *
+ * hsa_junction_text_device writes the text of a reduced table in hsa_sam_lines_device64's
+ * layout: d_line_off (n_rows + 1), d_out / out_cap, d_counters: [0] bytes wanted, [1] bytes
+ * written, [2] rows printed, [3] rows without a line (a chrID past n_chr or a motif past 6:
+ * none from the calls above). */
+#define HSA_JN_ROW_WORDS 8
+typedef struct {
+    int n_jobs;
+    uint32_t cigar_stride;
+    const uint32_t *d_rows;          /* hsa_splice_lines_batch_t's d_rows, d_cigar, d_line_stat after the call */
+    const uint32_t *d_cigar;
+    const uint32_t *d_line_stat;
+    uint32_t *d_jrows;               /* HSA_JN_ROW_WORDS u32 per row, row_cap rows, 16-byte aligned */
+    uint64_t n_have;                 /* rows the buffer holds already */
+    uint64_t row_cap;                /* at most 2^32 - 1 */
+    uint64_t *d_counters;
+} hsa_junction_rows_batch_t;
+int hsa_junction_rows_device(hsa_index_t *ix, const hsa_junction_rows_batch_t *b, void *stream);
+typedef struct {
+    uint32_t *d_jrows;               /* n_rows rows in, d_counters[1] rows out */
+    uint64_t n_rows;
+    uint64_t *d_counters;
+} hsa_junction_reduce_batch_t;
+int hsa_junction_reduce_device(hsa_index_t *ix, const hsa_junction_reduce_batch_t *b, void *stream);
+typedef struct {
+    const uint32_t *d_jrows;         /* a reduced table */
+    uint64_t n_rows;
+    const uint8_t *d_chr_names; const uint64_t *d_chr_off;   /* n_chr + 1 */
+    uint32_t n_chr;
+    uint32_t pad;
+    uint64_t *d_line_off;            /* n_rows + 1 */
+    uint8_t *d_out; uint64_t out_cap;
+    uint64_t *d_counters;
+} hsa_junction_text_batch_t;
+int hsa_junction_text_device(hsa_index_t *ix, const hsa_junction_text_batch_t *b, void *stream);
+
 /* ---- FASTQ bytes to a search batch ----
  * bwa_read_seq (bwaseqio.c:161-231) over kseq_read (kseq.h:155-193), and the filter and
  * per-read options at the top of bwa_cal_sa_reg_gap (bwtaln.c:313-332), for the raw bytes of
